@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — zstd block-decode hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload full_4a|huf_literals|raw_rle|full_4b|mix]
+    python bench.py --gpus N --steps K --warmup W [--workload full_4a|huf_literals|raw_rle|full_4b|mix] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (one cz_decode_batch_device call) over one batch of synthetic
 frames that already sits in HBM.  The call launches
@@ -51,7 +51,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E: 8.0 TB/s spec (6.29 TB/s measured copy)
 # What a SIMD of gfx950 issues, measured (profiles/r5/microbench_issue.txt, scripts/micro/issue.hip): with two or more waves one
 # integer VALU instruction of the kinds these kernels are made of (bit-field ops, funnel shifts, DPP, selects, SGPR operands) per
 # 4.2 clocks — the 2-clock rate holds for runs of plain VOP1 / VOP2 adds and logic ops on VGPRs only —, a lone wave one instruction
@@ -166,6 +166,45 @@ def _real_frames(n: int, level: int = 3, distinct: int = 384):
     return [frames[i % k] for i in range(n)], [origs[i % k] for i in range(n)], k
 
 
+DUMP_SAMPLE_BYTES = 10_000_000      # decoded bytes written by --dump-outputs over all ranks (float32: 40 MB)
+DUMP_MAX_FRAMES = 250_000           # result records written by --dump-outputs over all ranks (9 float64 fields: 18 MB)
+DUMP_SEED = 20_241_015
+
+
+def _dump_outputs(dump_dir: str, rank: int, world: int, t_out, t_res, regen: np.ndarray, out_off: np.ndarray, result_dtype) -> None:
+    """Writes what one decode_batch_device call handed back as dump_dir/<name>.npy (rank<r>_<name>.npy with N > 1): every field of
+    the per-frame result records (float64) and the decoded bytes (float32) — all of them when they fit this rank's share of
+    DUMP_SAMPLE_BYTES / DUMP_MAX_FRAMES, else a sorted sample drawn with a fixed seed, so two runs over the same batch read the same
+    positions.  Only bytes inside the frames' regenerated sizes are read (the gaps of the output layout are never written)."""
+    import torch
+    os.makedirs(dump_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    max_bytes, max_frames = DUMP_SAMPLE_BYTES // world, DUMP_MAX_FRAMES // world
+    n = regen.size
+    regen = regen.astype(np.int64)
+    total = int(regen.sum())
+    if total <= max_bytes:
+        pos = np.arange(total, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, max_bytes, dtype=np.int64))
+    end = np.cumsum(regen)
+    frame = np.searchsorted(end, pos, side="right")
+    addr = out_off.astype(np.int64)[frame] + pos - (end - regen)[frame]
+    decoded = t_out[torch.from_numpy(addr).to(t_out.device)].cpu().numpy().astype(np.float32)
+    np.save(os.path.join(dump_dir, f"{prefix}decoded_bytes.npy"), decoded)
+    res = t_res.cpu().numpy().view(result_dtype)
+    rows = np.arange(n) if n <= max_frames else np.sort(np.random.default_rng(DUMP_SEED).choice(n, max_frames, replace=False))
+    for name in result_dtype.names:
+        if name == "reserved":
+            continue
+        col = res[name][rows]
+        if col.ndim == 1:
+            np.save(os.path.join(dump_dir, f"{prefix}result_{name}.npy"), col.astype(np.float64))
+        else:
+            for k in range(col.shape[1]):
+                np.save(os.path.join(dump_dir, f"{prefix}result_{name}{k}.npy"), col[:, k].astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -186,9 +225,14 @@ def main():
     ap.add_argument("--real-frames", type=int, default=16000, help="frames of the real_libzstd_l3 entry of other_workloads (made by the box's libzstd at run time; 0: skip)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the real runs); gloo only to rehearse the N>1 code path on a box with fewer GPUs than ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step handed back (result records, decoded bytes: a fixed, seeded sample of them when "
+                         "there are more than fit 64 MB) as DIR/<name>.npy, float64 / float32; with N > 1, DIR/rank<r>_<name>.npy per rank")
     args = ap.parse_args()
     if args.frames is None:
         args.frames = 12500 if args.workload == "mix" else 10000
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     # ---- --gpus N without a launcher: start the N ranks ourselves (torch.distributed.run, one
     # process per GPU) BEFORE anything in this process touches the GPU, and exit with their code.
@@ -292,6 +336,9 @@ def main():
         return time.perf_counter() - t_begin
 
     elapsed = timed(decode)
+    if args.dump_outputs:
+        # what the last timed step left in the output and result buffers, before any later launch writes them again
+        _dump_outputs(args.dump_outputs, rank, world, t_out, t_res, batch.regen, out_off, cz.RESULT_DTYPE)
     # Per-launch kernel durations for the roofline: K more launches of the same step, each read
     # from the hipEvent pair the library records around the kernel on the stream it runs on
     # (reading a pair needs a sync, which must stay out of the timed region above).
@@ -608,12 +655,11 @@ def main():
             line["other_workloads"] = others
         if world == 1 and not args.no_other_workloads and chain_prepass:
             # two batches in flight: two contexts decode alternately without waiting for each other, in a process
-            # of its own (it needs GPU_MAX_HW_QUEUES=8 before the runtime starts: six streams on four hardware queues run one after
-            # the other).  A separate figure; `value` stays the one-batch-at-a-time rate.
+            # of its own with the hardware queues the environment gives it (six streams on fewer queues overlap less).  A separate
+            # figure; `value` stays the one-batch-at-a-time rate.
             import subprocess
             try:
-                pr = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "pipelined.py"), args.workload, str(F), "2"], capture_output=True, timeout=300,
-                                    env=dict(os.environ, GPU_MAX_HW_QUEUES="8"))
+                pr = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "pipelined.py"), args.workload, str(F), "2"], capture_output=True, timeout=300)
                 js = [l[5:] for l in pr.stdout.decode().splitlines() if l.startswith("JSON ")]
                 line["pipelined"] = json.loads(js[-1]) if js else {"error": pr.stderr.decode()[-300:]}
                 if js:

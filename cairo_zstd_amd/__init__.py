@@ -22,7 +22,7 @@ DEBUG_CHAIN_CPP_STEP, DEBUG_NO_HUF1, DEBUG_WX_POISON, DEBUG_EXEC_FIRST = 1, 2, 4
 from .status import CzError
 
 __all__ = ["Context", "FrameDecoder", "BlockDecodingStrategy", "decode_batch_host", "read_frame_header",
-           "read_block_header", "RESULT_DTYPE", "RESULT_FINISHED", "RESULT_HAS_CHECKSUM", "RESULT_CHECKSUM_COMPUTED",
+           "read_block_header", "graph_replay_available", "RESULT_DTYPE", "RESULT_FINISHED", "RESULT_HAS_CHECKSUM", "RESULT_CHECKSUM_COMPUTED",
            "RESULT_CHECKSUM_MATCH", "status", "CzError", "build", "lib"]
 
 
@@ -30,6 +30,11 @@ def _as_u8(b) -> np.ndarray:
     if isinstance(b, np.ndarray):
         return np.ascontiguousarray(b, dtype=np.uint8)
     return np.frombuffer(bytes(b), dtype=np.uint8)
+
+
+def graph_replay_available() -> bool:
+    """cz_graph_replay_available: whether a repeated launch can be captured as a hipGraph in this process (Context.set_graph_replay)."""
+    return bool(lib().cz_graph_replay_available())
 
 
 class Context:
@@ -162,7 +167,8 @@ class Context:
         lib().cz_context_set_early_execute(self._h, 1 if on else 0)
 
     def set_graph_replay(self, on: bool):
-        """on: a launch that repeats the one before it is captured as a hipGraph and replayed from then on; off (default): never."""
+        """on: a launch that repeats the one before it is captured as a hipGraph and replayed from then on, where
+        graph_replay_available(); off (default): never."""
         lib().cz_context_set_graph_replay(self._h, 1 if on else 0)
 
     def last_launch_was_replay(self) -> bool:

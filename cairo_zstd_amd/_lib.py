@@ -113,6 +113,8 @@ def lib() -> C.CDLL:
     L.cz_context_set_graph_replay.argtypes = [vp, C.c_int]
     L.cz_context_last_launch_was_replay.restype = C.c_int
     L.cz_context_last_launch_was_replay.argtypes = [vp]
+    L.cz_graph_replay_available.restype = C.c_int
+    L.cz_graph_replay_available.argtypes = []
     L.cz_context_last_small_ms.restype = C.c_int
     L.cz_context_last_small_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.cz_context_last_fallback_count.restype = C.c_int

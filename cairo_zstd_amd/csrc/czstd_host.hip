@@ -768,6 +768,16 @@ static int cz_replay(cz_context* c) {
     c->timed_small = c->g_timed_small; c->last_grid = c->g_grid; c->g_replayed = true;
     return CZ_OK;
 }
+/* A captured launch forks over three streams (the capture's own, stream2, stream3).  The HIP runtime gives a process
+   GPU_MAX_HW_QUEUES hardware queues (4 when unset) and puts streams beyond that on shared queues.  Captures were only ever made and
+   tested with a queue to spare (three streams on four queues); four streams on four queues — the early-execute arrangement — ended
+   in a host-side crash inside the ROCm 7.2 runtime.  So a launch is captured only when the process has more queues than the
+   capture has streams; otherwise every launch goes the ordinary way. */
+enum { CZ_CAPTURE_STREAMS = 3 };
+CZ_EXPORT int cz_graph_replay_available(void) {
+    static const int available = [] { const char* s = getenv("GPU_MAX_HW_QUEUES"); const int q = s ? atoi(s) : 0; return (q > 0 ? q : 4) > CZ_CAPTURE_STREAMS; }();
+    return available;
+}
 /* Captures the launch on a stream of the context's own (cz_enqueue does exactly what it does otherwise) and replays it at once.
    CZ_E_NOGRAPH: nothing was enqueued — the caller goes the ordinary way, and this context does not try again. */
 static int cz_capture(cz_context* c, const cz_batch_args& proto, size_t n) {
@@ -806,7 +816,7 @@ static int cz_launch(cz_context* c, const cz_batch_args& proto, size_t n) {
     if (n == 0) return CZ_OK;
     if (n > 0xFFFFFFFFull) return CZ_E_INVALID_ARG;
     /* (not the early-execute arrangement: capturing its four streams ended in a host-side crash inside the ROCm 7.2 runtime) */
-    const bool eligible = c->graph_mode && !c->g_bad && !proto.tasks && c->chain_arena && !c->early_execute;
+    const bool eligible = c->graph_mode && cz_graph_replay_available() && !c->g_bad && !proto.tasks && c->chain_arena && !c->early_execute;
     if (eligible) {
         if (c->g_exec && c->g_n == n && c->g_gen == c->cfg_gen && !memcmp(&c->g_proto, &proto, sizeof proto)) return cz_replay(c);
         if (c->g_seen && c->g_seen_n == n && c->g_seen_gen == c->cfg_gen && !memcmp(&c->g_seen_proto, &proto, sizeof proto)) {

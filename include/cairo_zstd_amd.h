@@ -229,8 +229,13 @@ int cz_context_last_fallback_count(cz_context* ctx, size_t* listed);
  * on = 1 turns that on; default 0: every launch is enqueued operation by operation (measured: 3 % of a Raw/RLE batch, 7 % of a
  * batch of 2 000 frames, nothing on the entropy-coded configurations — profiles/r5/graph_replay_ab.txt).  Nothing in the reference
  * corresponds to this: it is how the loop "decode the next batch into the same buffers" (src/frame_decoder.cairo:156-222 called
- * frame after frame) can be submitted here. */
+ * frame after frame) can be submitted here.  A launch is only captured where cz_graph_replay_available() says so; elsewhere
+ * every launch is enqueued operation by operation whatever `on` says. */
 int cz_context_set_graph_replay(cz_context* ctx, int on);
+/* 1 when launches can be captured in this process: the HIP runtime gives it more hardware queues (GPU_MAX_HW_QUEUES, 4 when
+ * unset) than a capture has streams (3).  With fewer, the streams of a capture share queues, an arrangement in which capturing
+ * crashed inside the ROCm 7.2 runtime. */
+int cz_graph_replay_available(void);
 /* 1 when the most recent batch launch was the replay of a captured graph. */
 int cz_context_last_launch_was_replay(const cz_context* ctx);
 /* The part of the most recent launch spent in cz_wexec_kernel (0 when it did not run). */

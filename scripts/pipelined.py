@@ -3,14 +3,14 @@
 batch alternately without waiting for each other: call i + 1's pre-pass (cz_chain_kernel: one wave per SIMD, most of the chip's issue
 slots idle) overlaps call i's execute stage.  Reports ms per batch in the steady state beside the one-batch-at-a-time figure.
 
-    GPU_MAX_HW_QUEUES=8 python scripts/pipelined.py [workload] [frames] [depth]
+    python scripts/pipelined.py [workload] [frames] [depth]
 
-(The runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues, 4 by default, and two streams on one queue run one
-after the other: two contexts x three streams need the larger number.  The script sets it itself when it is not set.)"""
+(The runtime multiplexes a process's streams onto the hardware queues it was given (GPU_MAX_HW_QUEUES), and two streams on one queue
+run one after the other: with fewer queues than two contexts x three streams, less of the second batch overlaps the first.  The
+script runs with whatever the environment sets; the figure it prints names the setting.)"""
 import os
 import sys
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))

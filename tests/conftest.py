@@ -8,7 +8,6 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE_CORPUS = "/root/reference/data/decode_corpus"  # only present in the build container
 
 
 def pytest_configure(config):

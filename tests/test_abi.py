@@ -27,6 +27,21 @@ def test_library_exports_every_declared_symbol():
     assert L.cz_abi_version() == 1
 
 
+def test_graph_replay_needs_a_hardware_queue_per_capture_stream():
+    """cz_graph_replay_available follows the hardware queues the HIP runtime gives the process (GPU_MAX_HW_QUEUES, 4 when unset):
+    a capture forks over three streams, and is only taken with a queue to spare."""
+    import subprocess
+    import sys
+    code = "import cairo_zstd_amd as cz; print(int(cz.graph_replay_available()))"
+    for value, want in ((None, "1"), ("2", "0"), ("1", "0")):
+        env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
+        if value is not None:
+            env["GPU_MAX_HW_QUEUES"] = value
+        p = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert p.stdout.strip().splitlines()[-1] == want, (value, p.stdout)
+
+
 def test_status_header_matches_python_names():
     assert cz.status.CZ_OK == 0 and cz.status.name(cz.status.CZ_E_SEQ_EXTRA_BITS) == "CZ_E_SEQ_EXTRA_BITS"
     assert len(set(cz.status.CODES.values())) == len(cz.status.CODES)

@@ -553,10 +553,16 @@ def test_repeated_launch_is_replayed_as_a_graph(cz):
     then on (cz_context_set_graph_replay(ctx, 1); off by default).  The replay must be the same work: outputs against the oracle before and
     after the BYTES behind the same pointers are replaced by another batch (a graph holds pointers and grids, never data); a
     change of the context's settings ends the replays until the new launch has repeated; with replay off nothing is captured;
-    the library's event times stay available in a replay (its events are event-record nodes of the graph)."""
+    the library's event times stay available in a replay (its events are event-record nodes of the graph).  Where the process has
+    too few hardware queues for a capture (cz_graph_replay_available() == 0) nothing is ever captured and every launch, the same
+    sequence of them, must still be right."""
     import torch
     from cairo_zstd_amd import synth
     dev = torch.device("cuda:0")
+    captures = cz.graph_replay_available()
+
+    def replays(*flags):
+        return [f and captures for f in flags]
     for kind, n in (("mix", 500), ("full_4a", 260), ("raw_rle", 300)):
         batches = [synth.generate(kind, n, first_index=fi) for fi in (5, 7001)]
         in_bytes = max(len(b.base) for b in batches)
@@ -597,18 +603,18 @@ def test_repeated_launch_is_replayed_as_a_graph(cz):
             load(batches[0])
             assert [run(c, batches[0], refs[0]) for _ in range(2)] == [False, False], kind   # (off by default)
             c.set_graph_replay(True)
-            assert [run(c, batches[0], refs[0]) for _ in range(4)] == [False, True, True, True], kind
+            assert [run(c, batches[0], refs[0]) for _ in range(4)] == replays(False, True, True, True), kind
             ms, chain = c.last_kernel_ms(), c.last_chain_ms()
-            assert 0.0 < chain <= ms, (kind, ms, chain)                 # (stamped by the replay itself)
+            assert 0.0 < chain <= ms, (kind, ms, chain)                 # (stamped by the replay itself where there is one)
             load(batches[1])                                            # other frames behind the same pointers
-            assert [run(c, batches[1], refs[1]) for _ in range(2)] == [True, True], kind
+            assert [run(c, batches[1], refs[1]) for _ in range(2)] == replays(True, True), kind
             c.set_verify_checksum(True)                                 # the context changed: an ordinary launch, then a new graph
-            assert [run(c, batches[1], refs[1]) for _ in range(3)] == [False, True, True], kind
+            assert [run(c, batches[1], refs[1]) for _ in range(3)] == replays(False, True, True), kind
             c.set_graph_replay(False)
             assert [run(c, batches[1], refs[1]) for _ in range(3)] == [False, False, False], kind
             c.set_graph_replay(True)
             load(batches[0])
-            assert [run(c, batches[0], refs[0]) for _ in range(3)] == [False, True, True], kind
+            assert [run(c, batches[0], refs[0]) for _ in range(3)] == replays(False, True, True), kind
         finally:
             c.close()
 

@@ -4,7 +4,8 @@ Vectors (data only) come from the reference's tests:
   * src/tests/bit_reader.cairo:14-16,56-58   16-byte constant + chunk schedule
   * src/tests/utils.cairo:134-150            14 XXH64 known answers (seed 0)
   * src/decoding/sequence_section_decoder.cairo:707-737   5 predefined-LL table entries
-  * data/decode_corpus                        (original, .zst) pairs -> tests/golden/decode_corpus
+  * data/decode_corpus                        (original, .zst) pairs -> tests/golden/decode_corpus, the .zst side of the large
+                                              ones -> tests/golden/decode_corpus_large (manifest: hashes of all 100 originals)
 """
 import ctypes as C
 import hashlib
@@ -15,7 +16,7 @@ import numpy as np
 import pytest
 
 import oracle
-from conftest import GOLDEN, REFERENCE_CORPUS
+from conftest import GOLDEN
 from cairo_zstd_amd import status
 
 CONST16 = bytes.fromhex("C141080000ECC8964279D4BCF72CD548")  # ba.append_word(0xC141..., 16): big-endian bytes
@@ -156,11 +157,14 @@ def test_corpus_manifest_matches_fixtures(golden_corpus):
         assert int(m["xxh64"], 16) == oracle.xxh64(orig)
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_CORPUS), reason="full reference corpus only exists in the build container")
 def test_corpus_full_reference_tree():
+    """Every frame of the reference's corpus: the small pairs are under decode_corpus, the compressed side of the large ones
+    under decode_corpus_large; the manifest holds what the reference's originals hash to."""
     man = json.load(open(os.path.join(GOLDEN, "decode_corpus_manifest.json")))
+    assert len(man) == 100
     for name, m in man.items():
-        z = open(os.path.join(REFERENCE_CORPUS, name + ".zst"), "rb").read()
+        z = open(os.path.join(GOLDEN, "decode_corpus" if m["committed"] else "decode_corpus_large", name + ".zst"), "rb").read()
+        assert hashlib.sha256(z).hexdigest() == m["zst_sha256"], name
         st, out, info = oracle.decode_frame(z, cap=m["orig_len"] + 64)
         assert st == 0, name
         assert hashlib.sha256(out).hexdigest() == m["orig_sha256"], name
