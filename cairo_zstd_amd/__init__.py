@@ -94,6 +94,17 @@ class Context:
         if st:
             raise CzError(st, "cz_context_set_dictionary")
 
+    def set_dictionaries(self, dicts, no_id: "Dictionary | None" = None):
+        """Batch decodes pick each frame's dictionary by the Dictionary_ID of its header: the one of `dicts` with that ID, `no_id`
+        for frames without an ID (None: no dictionary); any other ID fails the frame with CZ_E_DICT_UNKNOWN (detail[0] = the ID).
+        An empty `dicts` with no `no_id` clears the setting.  Replaces set_dictionary's setting and is replaced by it."""
+        dicts = list(dicts)
+        arr = (C.c_void_p * max(len(dicts), 1))(*[d._h if d is not None else None for d in dicts])
+        st = lib().cz_context_set_dictionaries(self._h, arr if dicts else None, len(dicts), no_id._h if no_id is not None else None)
+        if st:
+            raise CzError(st, "cz_context_set_dictionaries")
+        self._dict = (dicts, no_id)                                      # keep them alive while launches use them
+
     def last_chain_ms(self) -> float:
         """Milliseconds of the last launch spent in the FSE-chain pre-pass kernel (0 when it is off)."""
         ms = C.c_float(0)

@@ -38,7 +38,7 @@ class BlockHeader(C.Structure):
 
 def build(force: bool = False) -> str:
     """Compile the library in-tree with hipcc for gfx950 (csrc/Makefile)."""
-    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_types.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_types.h", "czstd_dict.h")]
     srcs += [os.path.join(_HERE, "..", "include", f) for f in ("cairo_zstd_amd.h", "cairo_zstd_amd_status.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -207,6 +207,8 @@ def lib() -> C.CDLL:
     L.cz_dictionary_offset_hist.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.cz_context_set_dictionary.restype = C.c_int
     L.cz_context_set_dictionary.argtypes = [vp, vp]
+    L.cz_context_set_dictionaries.restype = C.c_int
+    L.cz_context_set_dictionaries.argtypes = [vp, C.POINTER(vp), sz, vp]
     L.cz_decoder_scratch_init_from_dict.restype = C.c_int
     L.cz_decoder_scratch_init_from_dict.argtypes = [vp, vp]
     L.cz_frame_decoder_scratch.restype = vp

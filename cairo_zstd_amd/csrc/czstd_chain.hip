@@ -30,6 +30,8 @@
  * (frame_first[f] = 0) and the main kernel decodes that frame entirely by itself, producing the
  * reference's status codes in the reference's order.  Nothing here reports errors.
  */
+#include "czstd_dict.h"   /* the table of cz_context_set_dictionaries and its lookup (cz_scan_kernel) */
+
 #ifndef CZC_SLOTS
 #define CZC_SLOTS 10        /* 40 chains per CU = 10 240 on the chip; 12 also fit the LDS, but leave no room for cz_huf1_kernel next to this kernel */
 #endif
@@ -597,6 +599,18 @@ __device__ static inline void czs_begin(CzsWalk& w, const uint8_t* src, uint64_t
     if (!single) { const uint32_t wd = (uint32_t)(h0 >> 40) & 0xFF; const uint64_t base = 1ull << (10 + (wd >> 3)); if (base + (base / 8) * (wd & 7) >= 4123168604160ull) return; }
     w.pos = hl; w.active = 1; w.has_checksum = (d >> 2) & 1; w.h8 = czs_ld8_issue(src, len, hl, &w.h8sh);
 }
+/* cz_context_set_dictionaries (a.dicts): a frame whose complete header names an ID the table does not have is not walked — nothing is
+   listed for it and its result record is not written here (a frame of Raw / RLE blocks would otherwise be finished by the pre-pass and
+   come back as a success): cz_decode_frames_kernel reports CZ_E_DICT_UNKNOWN.  Kept out of czs_begin, which cz_wexec_kernel shares. */
+__device__ static inline void czs_dict_check(CzsWalk& w, const cz_dict_entry* dicts, uint32_t ndicts) {
+    if (!w.active) return;
+    const uint64_t h0 = czs_ld8(w.src, w.len, 0);
+    const uint32_t d = (uint32_t)(h0 >> 32) & 0xFF, didf = d & 3, dl = didf == 3 ? 4 : didf, at = 5 + (((d >> 5) & 1) ? 0 : 1);
+    uint32_t id = (uint32_t)(h0 >> (8 * at));                           /* bytes at..7 */
+    if (at + dl > 8) id |= (uint32_t)(czs_ld8(w.src, w.len, 8) << (8 * (8 - at)));   /* a 4-byte field that ends past byte 7 (the header is complete: len >= at + dl) */
+    id = dl == 0 ? 0u : (dl == 4 ? id : id & ((1u << (8 * dl)) - 1u));
+    if (cz_dict_find(dicts, ndicts, id) == CZ_DICT_UNKNOWN) { w.active = 0; w.ok = 0; }
+}
 /* advances to the next block: 1 with `b` filled, or 0 — the walk is over (w.active = 0) and w.ok says whether the frame was
    regular to its end */
 __device__ static inline int czs_next(CzsWalk& w, uint32_t chain_min_nseq, CzsBlk& b) {
@@ -709,6 +723,7 @@ extern "C" __global__ void __launch_bounds__(CZ_WG_THREADS) cz_scan_kernel(cz_ba
     const int valid = f < a.n;
     CzsWalk w;
     czs_begin(w, valid ? a.in_base + a.in_off[f] : nullptr, valid ? a.in_len[f] : 0, valid);
+    if (a.dicts) czs_dict_check(w, a.dicts, a.ndicts);
     CzsBlk b; b.type = b.blk_off = b.bsize = b.lt = b.regen = b.lit_hdr = b.nseq = b.sbody = b.modes = 0;
     const uint64_t ocap = valid ? a.out_cap[f] : 0;
     const int with_lits = a.lit_arena != nullptr;                       /* literal and copy lists only with a literal arena (cz_context_set_literal_arena) */

@@ -78,7 +78,8 @@ struct cz_context {
     hipStream_t stream = nullptr; bool own_stream = false;
     int num_cu = 0, occupancy = 0, grid_max = 0;
     uint8_t* lit_scratch = nullptr; int lit_slots = 0; uint32_t* work_counter = nullptr;
-    const struct cz_dictionary* batch_dict = nullptr;                   /* cz_context_set_dictionary */
+    const struct cz_dictionary* batch_dict = nullptr;                   /* cz_context_set_dictionary; with dict_table: the no-ID dictionary */
+    cz_dict_entry* dict_table = nullptr; uint32_t dict_count = 0;       /* cz_context_set_dictionaries: the table in HBM (sorted by ID; NULL: not in that mode) */
     hipEvent_t ev_start = nullptr, ev_mid = nullptr, ev_mid2 = nullptr, ev_stop = nullptr; bool timed = false, timed_chain = false, timed_exec = false;
     bool wexec_kernel = true;              /* far-offset batches: cz_wexec_kernel (a workgroup per frame, window in LDS) side by side with cz_execute_frames_kernel */
     int wexec_cus = 0;                     /* CUs (= workgroups) cz_wexec_kernel runs on; 0: half of them */
@@ -188,6 +189,7 @@ CZ_EXPORT void cz_context_destroy(cz_context* c) {
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->d_prof) (void)hipFree(c->d_prof);
     if (c->chain_arena) (void)hipFree(c->chain_arena);
+    if (c->dict_table) (void)hipFree(c->dict_table);
     if (c->lit_arena) (void)hipFree(c->lit_arena);
     if (c->lit_first) (void)hipFree(c->lit_first);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -514,6 +516,7 @@ static int cz_enqueue(cz_context* c, const cz_batch_args& proto, size_t n, hipSt
     a.n = (uint32_t)n; a.work_counter = c->work_counter; a.lit_scratch = c->lit_scratch; a.lit_scratch_stride = CZ_WG_SCRATCH_BYTES;
     a.prof = c->d_prof; a.verify_checksum = a.tasks ? 0 : c->verify_checksum; a.debug_flags = c->debug_flags;
     if (!a.tasks && c->batch_dict) { a.dict_state = c->batch_dict->d_state; a.dict = c->batch_dict->d_raw + c->batch_dict->content_off; a.dict_len = c->batch_dict->len - c->batch_dict->content_off; }
+    if (!a.tasks && c->dict_table) { a.dicts = c->dict_table; a.ndicts = c->dict_count; }
     int grid = (int)(n < (size_t)c->grid_max ? n : (size_t)c->grid_max);
 #ifdef CZ_EXPERIMENT
     if (const char* e = getenv("CZ_GRID_PER_CU")) { const int g = atoi(e) * c->num_cu; if (g > 0 && g < grid) grid = g; }
@@ -567,7 +570,7 @@ static int cz_enqueue(cz_context* c, const cz_batch_args& proto, size_t n, hipSt
             a.lit_segs = c->lit_segs; a.lit_seg_capacity = c->seg_capacity; a.copy_segs = c->copy_segs; a.copy_seg_capacity = c->seg_capacity; a.frame_pre = c->frame_pre;
         }
         /* which kernels the execute stage has is settled BEFORE the scan, so that every kernel of the batch sees the same wx_list */
-        const bool use_exec = c->exec_kernel && lit_pass && !c->batch_dict;
+        const bool use_exec = c->exec_kernel && lit_pass && !c->batch_dict && !c->dict_table;
         bool use_wx = use_exec && c->wexec_kernel;
         if (use_wx && !c->wexec_ready) {
             if (cap) return CZ_E_NOGRAPH;
@@ -1282,8 +1285,33 @@ CZ_EXPORT int cz_context_set_dictionary(cz_context* c, const cz_dictionary* d) {
     CZ_HIP(c, hipStreamSynchronize(c->stream));
     c->cfg_gen++;
     c->batch_dict = d;
+    if (c->dict_table) { (void)hipFree(c->dict_table); c->dict_table = nullptr; c->dict_count = 0; }   /* (the two calls replace each other) */
     return CZ_OK;
 }
+/* Batch decodes of this context pick each frame's dictionary by the Dictionary_ID of its header: `dicts` (k of them, IDs distinct and
+   not 0), `no_id` for frames without an ID (NULL: none), CZ_E_DICT_UNKNOWN for any other ID.  The table is uploaded here, sorted by ID
+   (cz_dict_find).  Any error leaves the previous setting in force. */
+CZ_EXPORT int cz_context_set_dictionaries(cz_context* c, const cz_dictionary* const* dicts, size_t k, const cz_dictionary* no_id) try {
+    if (!c || (k && !dicts) || k > CZ_MAX_DICTIONARIES || (no_id && no_id->ctx != c)) return CZ_E_INVALID_ARG;
+    std::vector<cz_dict_entry> t(k);
+    for (size_t i = 0; i < k; i++) {
+        const cz_dictionary* d = dicts[i];
+        if (!d || d->ctx != c || d->id == 0) return CZ_E_INVALID_ARG;
+        t[i].id = d->id; t[i].pad = 0; t[i].state = d->d_state; t[i].content = d->d_raw + d->content_off; t[i].content_len = d->len - d->content_off;
+    }
+    std::sort(t.begin(), t.end(), [](const cz_dict_entry& x, const cz_dict_entry& y) { return x.id < y.id; });
+    for (size_t i = 1; i < k; i++) if (t[i].id == t[i - 1].id) return CZ_E_INVALID_ARG;
+    CZ_HIP(c, hipSetDevice(c->device));
+    CZ_HIP(c, hipStreamSynchronize(c->stream));                         /* launches in flight may still read the old table */
+    if (!k && !no_id) return cz_context_set_dictionary(c, nullptr);
+    cz_dict_entry* table = nullptr;                                     /* (k == 0: one unused entry, so that the kernels see a table) */
+    CZ_HIP(c, hipMalloc((void**)&table, (k ? k : 1) * sizeof(cz_dict_entry)));
+    if (k && hipMemcpy(table, t.data(), k * sizeof(cz_dict_entry), hipMemcpyHostToDevice) != hipSuccess) { c->last_hip_error = (int)hipGetLastError(); (void)hipFree(table); return CZ_E_HIP; }
+    if (c->dict_table) (void)hipFree(c->dict_table);
+    c->cfg_gen++;
+    c->dict_table = table; c->dict_count = (uint32_t)k; c->batch_dict = no_id;
+    return CZ_OK;
+} catch (const std::bad_alloc&) { return CZ_E_OUT_OF_MEMORY; }
 CZ_EXPORT uint32_t cz_dictionary_id(const cz_dictionary* d) { return d ? d->id : 0; }
 CZ_EXPORT size_t cz_dictionary_content_len(const cz_dictionary* d) { return d ? d->len - d->content_off : 0; }
 CZ_EXPORT int cz_dictionary_offset_hist(const cz_dictionary* d, uint32_t out[3]) {

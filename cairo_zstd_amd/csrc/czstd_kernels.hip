@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "czstd_types.h"
+#include "czstd_dict.h"
 
 #define LANE ((int)(threadIdx.x & 63u))   /* lane of the wavefront (cz_huf_kernel, which shares this file's helpers, has workgroups of several waves) */
 #define CZ_NOINLINE __attribute__((noinline))
@@ -2684,11 +2685,38 @@ extern "C" __global__ void __launch_bounds__(CZ_WG_THREADS, CZ_MAIN_WAVES) cz_de
             io.src = (cz_gcptr)(a.in_base + a.in_off[f]); io.src_len = a.in_len[f]; io.dst = (cz_gptr)(a.out_base + a.out_off[f]); io.dst_cap = a.out_cap[f];
             io.produced = 0; io.drained = 0; io.window = 0; io.parse_header = 1; io.has_checksum = 0;
             io.strategy = 0; io.strategy_n = 0; io.streaming = 0; io.verify = a.verify_checksum; io.dict = (cz_gcptr)a.dict; io.dict_len = a.dict_len;
+            const cz_device_frame_state* dstate = a.dict_state;
+            if (a.dicts) {
+                /* cz_context_set_dictionaries: the frame's Dictionary_ID picks the entry (a.dict_state / a.dict: the no-ID dictionary).  Only a
+                   complete header is looked at — one that is not reports its error from cz_run_frame, as without a table — and an ID the
+                   table does not have ends the frame here, before any block: CZ_E_DICT_UNKNOWN, detail[0] the ID, nothing written */
+                __syncthreads();
+                if (LANE == 0) {
+                    uint32_t pick = CZ_DICT_NO_ID, id = 0;
+                    if (cz_parse_frame_header(io.src, io.src_len, sh.bc) == 0) { id = cz_frame_dict_id(io.src); pick = cz_dict_find(a.dicts, a.ndicts, id); }
+                    sh.frame_idx = pick; sh.bc.d0 = id;
+                }
+                __syncthreads();
+                const uint32_t pick = cz_uni(sh.frame_idx);
+                if (pick == CZ_DICT_UNKNOWN) {
+                    if (LANE == 0) {
+                        CZ_GLOBAL cz_frame_result* res = (CZ_GLOBAL cz_frame_result*)&a.results[f];
+                        res->status = CZ_E_DICT_UNKNOWN; res->blocks_decoded = 0; res->bytes_consumed = sh.bc.hdr_len; res->bytes_produced = 0;
+                        res->checksum_from_data = 0; res->flags = 0; res->calculated_checksum = 0; res->reserved = 0;
+                        res->detail[0] = sh.bc.d0; res->detail[1] = sh.bc.hdr_len;
+                    }
+                    continue;
+                }
+                if (pick != CZ_DICT_NO_ID) {
+                    const cz_dict_entry* e = a.dicts + pick;
+                    dstate = e->state; io.dict = (cz_gcptr)e->content; io.dict_len = e->content_len;
+                }
+            }
             cz_state_reset();
-            if (a.dict_state) {
+            if (dstate) {
                 /* every frame of the batch starts as DecoderScratch::init_from_dict leaves a workspace (scratch.cairo:60-65):
                    the dictionary's tables and repeat offsets; its Huffman table goes to this workgroup's carried-table slot */
-                CZ_GLOBAL const cz_device_frame_state* ds = (CZ_GLOBAL const cz_device_frame_state*)a.dict_state;
+                CZ_GLOBAL const cz_device_frame_state* ds = (CZ_GLOBAL const cz_device_frame_state*)dstate;
                 __syncthreads();
                 for (uint32_t i = (uint32_t)LANE; i < 512; i += 64) { CZ_FSE_LL[i] = ds->fse[0][i]; CZ_FSE_ML[i] = ds->fse[2][i]; }
                 for (uint32_t i = (uint32_t)LANE; i < 256; i += 64) CZ_FSE_OF[i] = ds->fse[1][i];

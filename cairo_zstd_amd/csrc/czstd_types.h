@@ -175,6 +175,9 @@ typedef struct cz_batch_args {
     uint32_t wx_cus;                          /* workgroups of cz_wexec_kernel that stay (a launch may have more: any beyond this many leave at once); cz_execute_frames_kernel's waves
                                                  on even CUs wait for that many to be in place (cz_cu_side).  (Kept at the END of the struct: the offsets of the fields above
                                                  decide how the compiler spills the execute kernels' scalar registers, and 0.1 ms of config 4a with them: profiles/r5/NOTES.md) */
+    /* (appended for the same reason) */
+    const struct cz_dict_entry* dicts; uint32_t ndicts;   /* cz_context_set_dictionaries: the table (sorted by ID) the frames pick from by Dictionary_ID,
+                                                             dict_state / dict / dict_len then carry the no-ID dictionary; NULL: no table */
 } cz_batch_args;
 
 #endif

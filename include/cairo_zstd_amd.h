@@ -183,7 +183,7 @@ int cz_context_last_exec_ms(cz_context* ctx, float* ms);
 /* With both arenas set, frames the pre-pass prepared completely are executed by cz_execute_frames_kernel (one wave per
  * frame, sequence execution only: no decoders in LDS or registers) — on = 1, the default; on = 0 sends them to
  * cz_decode_frames_kernel's record path instead (the round-2 arrangement, kept for A/B runs: bench.py --no-exec-kernel).
- * Batches that start from a dictionary (cz_context_set_dictionary) always take cz_decode_frames_kernel. */
+ * Batches that start from a dictionary (cz_context_set_dictionary / cz_context_set_dictionaries) always take cz_decode_frames_kernel. */
 int cz_context_set_exec_kernel(cz_context* ctx, int on);   /* (on = 4 / 8: that register budget — waves per SIMD — whatever the batch looks like; 1: decided on the device) */
 /* With both arenas set, the frames that hold enough sequences to be worth a workgroup can also be executed by cz_wexec_kernel:
  * 16 waves per frame, the output of the block in hand in a 128 KiB LDS window (earlier blocks are read from the output buffer;
@@ -349,6 +349,19 @@ int  cz_decoder_scratch_init_from_dict(cz_decoder_scratch* workspace, const cz_d
  * whose first block leans on the dictionary's tables are decoded by cz_decode_frames_kernel alone (the pre-pass lists only
  * frames that define their own tables), the others take the pre-pass as usual.  The dictionary must outlive the launches. */
 int  cz_context_set_dictionary(cz_context* ctx, const cz_dictionary* d);
+/* Several dictionaries at once (libzstd's ZSTD_d_refMultipleDDicts): every later cz_decode_batch_* on this context (per context in
+ * cz_decode_batch_multi*, and cz_decode_stream) picks each frame's dictionary by the Dictionary_ID of its header (frame.cairo:207-225):
+ *   no ID field, or ID 0       -> no_id_dict, as init_from_dict leaves a workspace (NULL: no dictionary, a fresh workspace)
+ *   cz_dictionary_id(dicts[j]) -> dicts[j]: its tables, its three repeat offsets, its content
+ *   any other ID               -> CZ_E_DICT_UNKNOWN, detail[0] = the ID, bytes_produced = 0, the frame's output region untouched.
+ * Header errors come first, as always (a truncated ID field is CZ_E_FH_DICT_ID_READ, a skippable frame CZ_E_FH_SKIP_FRAME);
+ * CZ_E_DICT_UNKNOWN is reported after a complete header, before any block.  CZ_E_INVALID_ARG when dicts is NULL with k > 0, an entry
+ * is NULL, a dictionary belongs to another context, a listed dictionary has ID 0 (it can only be no_id_dict), two listed ones share
+ * an ID, or k > CZ_MAX_DICTIONARIES; on any error the previous setting stays in force.  k == 0 with no_id_dict NULL clears the
+ * setting, like cz_context_set_dictionary(ctx, NULL); the two calls replace each other.  Synchronises the context's stream; the
+ * dictionaries must outlive the launches.  Such batches, like those of cz_context_set_dictionary, take cz_decode_frames_kernel. */
+#define CZ_MAX_DICTIONARIES 1024
+int  cz_context_set_dictionaries(cz_context* ctx, const cz_dictionary* const* dicts, size_t k, const cz_dictionary* no_id_dict);
 
 /* BlockDecoder (src/decoding/block_decoder.cairo:20-30): a plain value like the reference's struct. */
 typedef struct cz_block_decoder {
