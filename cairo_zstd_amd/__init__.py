@@ -5,7 +5,8 @@ Python here is a thin mirror over the C ABI (include/cairo_zstd_amd.h, libcairo_
   * Context / decode_batch* : many independent frames per launch (the GPU hot path)
   * FrameDecoder            : FrameDecoderTrait call for call (src/frame_decoder.cairo:107-335)
   * read_frame_header / read_block_header : stateless parsers
-All decoding runs in the HIP kernels; nothing here decodes on the CPU.
+  * compress / compress_batch_host / Context.compress_batch_device : batched compression on the device
+All decoding and compression runs in the HIP kernels; nothing here decodes or compresses on the CPU.
 """
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import status
-from ._lib import (RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
+from ._lib import (COMPRESS_CHECKSUM, COMPRESS_RESULT_DTYPE, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
                    BlockHeader, FrameHeader, build, lib)
 
 DEBUG_CHAIN_CPP_STEP, DEBUG_NO_HUF1, DEBUG_WX_POISON, DEBUG_EXEC_FIRST = 1, 2, 4, 8     # cz_context_set_debug_flags
@@ -23,7 +24,8 @@ from .status import CzError
 
 __all__ = ["Context", "FrameDecoder", "BlockDecodingStrategy", "decode_batch_host", "read_frame_header",
            "read_block_header", "graph_replay_available", "RESULT_DTYPE", "RESULT_FINISHED", "RESULT_HAS_CHECKSUM", "RESULT_CHECKSUM_COMPUTED",
-           "RESULT_CHECKSUM_MATCH", "status", "CzError", "build", "lib"]
+           "RESULT_CHECKSUM_MATCH", "status", "CzError", "build", "lib", "compress_bound", "compress_batch_host", "compress",
+           "COMPRESS_CHECKSUM", "COMPRESS_RESULT_DTYPE"]
 
 
 def _as_u8(b) -> np.ndarray:
@@ -252,6 +254,61 @@ class Context:
         if st:
             raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
         return out, res
+
+    def compress_batch_device(self, in_base: int, in_off: int, in_len: int, n: int, out_base: int, out_off: int,
+                              out_cap: int, results: int, checksum: bool = False):
+        """cz_compress_batch_device.  All arguments are raw DEVICE pointers (tensor.data_ptr()); `results` holds n
+        COMPRESS_RESULT_DTYPE records.  Asynchronous on the context's stream, like decode_batch_device."""
+        st = lib().cz_compress_batch_device(self._h, in_base, in_off, in_len, n, out_base, out_off, out_cap,
+                                            COMPRESS_CHECKSUM if checksum else 0, results)
+        if st:
+            raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
+
+    def compress_batch_host(self, in_base, in_off, in_len, out_off, out_cap, out: np.ndarray, checksum: bool = False):
+        """cz_compress_batch_host: host buffers in, `out` (uint8, written in place) out.  Returns the result records."""
+        in_base = _as_u8(in_base)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        in_len = np.ascontiguousarray(in_len, dtype=np.uint64)
+        out_off = np.ascontiguousarray(out_off, dtype=np.uint64)
+        out_cap = np.ascontiguousarray(out_cap, dtype=np.uint64)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"]
+        n = int(in_off.size)
+        res = np.zeros(n, dtype=COMPRESS_RESULT_DTYPE)
+        st = lib().cz_compress_batch_host(self._h, in_base.ctypes.data if in_base.size else None, in_base.size, in_off.ctypes.data,
+                                          in_len.ctypes.data, n, out.ctypes.data, out.size, out_off.ctypes.data, out_cap.ctypes.data,
+                                          COMPRESS_CHECKSUM if checksum else 0, res.ctypes.data)
+        if st:
+            raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
+        return res
+
+
+def compress_bound(n: int) -> int:
+    """cz_compress_bound: the largest frame cz_compress_batch_* writes for n input bytes."""
+    return int(lib().cz_compress_bound(n))
+
+
+def compress_batch_host(buffers, ctx: Context, checksum: bool = False):
+    """Compresses every buffer into one zstd frame, in one launch: list of (result record, frame bytes)."""
+    lens = np.array([len(b) for b in buffers], dtype=np.uint64)
+    in_off = np.zeros(len(buffers), dtype=np.uint64)
+    if len(buffers) > 1:
+        in_off[1:] = np.cumsum(lens[:-1])
+    in_base = np.frombuffer(b"".join(bytes(b) for b in buffers) + b"\0" * 16, dtype=np.uint8)
+    caps = np.array([compress_bound(int(n)) for n in lens], dtype=np.uint64)
+    out_off = np.zeros(len(buffers), dtype=np.uint64)
+    if len(buffers) > 1:
+        out_off[1:] = np.cumsum(caps[:-1])
+    out = np.zeros(max(int(caps.sum()), 1), dtype=np.uint8)
+    res = ctx.compress_batch_host(in_base, in_off, lens, out_off, caps, out, checksum=checksum)
+    return [(res[i], out[int(out_off[i]): int(out_off[i]) + int(res[i]["bytes_written"])].tobytes()) for i in range(len(buffers))]
+
+
+def compress(data, ctx: Context, checksum: bool = False) -> bytes:
+    """One buffer -> one zstd frame (through the batched kernel)."""
+    (r, frame), = compress_batch_host([data], ctx, checksum=checksum)
+    if int(r["status"]):
+        raise CzError(int(r["status"]), "cz_compress_batch_host")
+    return frame
 
 
 def decode_batch_host(frames, caps, ctx: Context | None = None):

@@ -18,6 +18,11 @@ RESULT_DTYPE = np.dtype([("status", "<i4"), ("blocks_decoded", "<u4"), ("bytes_c
                          ("bytes_produced", "<u8"), ("checksum_from_data", "<u4"), ("flags", "<u4"),
                          ("detail", "<u8", (2,)), ("calculated_checksum", "<u4"), ("reserved", "<u4")])
 RESULT_FINISHED, RESULT_HAS_CHECKSUM, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH = 1, 2, 4, 8
+# cz_compress_result (32 bytes), one per buffer of a batched compression
+COMPRESS_RESULT_DTYPE = np.dtype([("status", "<i4"), ("blocks", "<u4"), ("bytes_read", "<u8"), ("bytes_written", "<u8"),
+                                  ("checksum", "<u4"), ("flags", "<u4")])
+assert COMPRESS_RESULT_DTYPE.itemsize == 32
+COMPRESS_CHECKSUM = 1
 
 
 class FrameHeader(C.Structure):
@@ -38,7 +43,7 @@ class BlockHeader(C.Structure):
 
 def build(force: bool = False) -> str:
     """Compile the library in-tree with hipcc for gfx950 (csrc/Makefile)."""
-    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_types.h", "czstd_dict.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_enc.hip", "czstd_types.h", "czstd_dict.h")]
     srcs += [os.path.join(_HERE, "..", "include", f) for f in ("cairo_zstd_amd.h", "cairo_zstd_amd_status.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -137,6 +142,12 @@ def lib() -> C.CDLL:
     L.cz_decode_batch_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp]
     L.cz_decode_batch_host.restype = C.c_int
     L.cz_decode_batch_host.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp]
+    L.cz_compress_bound.restype = C.c_uint64
+    L.cz_compress_bound.argtypes = [C.c_uint64]
+    L.cz_compress_batch_device.restype = C.c_int
+    L.cz_compress_batch_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, C.c_uint32, vp]
+    L.cz_compress_batch_host.restype = C.c_int
+    L.cz_compress_batch_host.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, C.c_uint32, vp]
     L.cz_partition_balanced.restype = C.c_int
     L.cz_partition_balanced.argtypes = [vp, sz, sz, vp]
     L.cz_decode_batch_multi.restype = C.c_int

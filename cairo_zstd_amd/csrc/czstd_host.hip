@@ -31,6 +31,7 @@
 #include "czstd_chain.hip"
 #include "czstd_pre.hip"
 #include "czstd_wexec.hip"
+#include "czstd_enc.hip"     /* cz_compress_frames_kernel */
 #ifdef CZ_EXP_PAD   /* diagnostic: shifts the code objects behind it by CZ_EXP_PAD x 256 bytes (does the layout of the kernels in the code object matter?) */
 extern "C" __global__ void cz_pad_kernel(uint32_t* p) {
 #pragma unroll
@@ -95,6 +96,8 @@ struct cz_context {
     uint32_t* fallback_list = nullptr;                                  /* n entries, allocated with frame_first */
     int last_grid = 0;
     int last_hip_error = 0, last_hip_line = 0;
+    /* batched compression (cz_compress_batch_*): per-workgroup scratch of cz_compress_frames_kernel, allocated by the first call */
+    uint8_t* enc_scratch = nullptr; int enc_slots = 0; uint32_t* enc_counter = nullptr; int enc_grid = 0;
     /* staging for cz_decode_batch_host */
     void* d_stage = nullptr; size_t d_stage_bytes = 0;
     void* h_pin = nullptr; size_t h_pin_bytes = 0;                      /* pinned host staging of cz_decode_batch_multi's share */
@@ -184,6 +187,8 @@ CZ_EXPORT void cz_context_destroy(cz_context* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->lit_scratch) (void)hipFree(c->lit_scratch);
+    if (c->enc_scratch) (void)hipFree(c->enc_scratch);
+    if (c->enc_counter) (void)hipFree(c->enc_counter);
     if (c->work_counter) (void)hipFree(c->work_counter);
     if (c->d_stage) (void)hipFree(c->d_stage);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
@@ -916,6 +921,74 @@ CZ_EXPORT int cz_decode_batch_host(cz_context* c, const void* in_base, size_t in
     if (st) return st;
     CZ_HIP(c, hipMemcpyAsync(out_base, d + o_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
     CZ_HIP(c, hipMemcpyAsync(results, d + o_res, n * sizeof(cz_frame_result), hipMemcpyDeviceToHost, c->stream));
+    CZ_HIP(c, hipStreamSynchronize(c->stream));
+    return CZ_OK;
+}
+
+/* ------------------------------------------------------------------ compression */
+CZ_EXPORT uint64_t cz_compress_bound(uint64_t src_len) {
+    const uint64_t blocks = src_len ? (src_len + CZE_BLOCK - 1) / CZE_BLOCK : 1;
+    return 14 + 4 + 3 * blocks + src_len;              /* largest frame header, a Raw block header per block, the checksum */
+}
+
+CZ_EXPORT int cz_compress_batch_device(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
+                                       void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
+                                       cz_compress_result* d_results) {
+    if (!c || (flags & ~CZ_COMPRESS_CHECKSUM) || n > 0xFFFFFFFFull) return CZ_E_INVALID_ARG;
+    if (n == 0) return CZ_OK;
+    if (!d_in_base || !d_in_off || !d_in_len || !d_out_base || !d_out_off || !d_out_cap || !d_results) return CZ_E_INVALID_ARG;
+    CZ_HIP(c, hipSetDevice(c->device));
+    if (!c->enc_grid) {                                                 /* workgroups of ~80 KB of LDS: as many as fit on every CU */
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_frames_kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
+        c->enc_grid = c->num_cu * occ;
+    }
+    const int grid = (size_t)c->enc_grid < n ? c->enc_grid : (int)n;
+    if (c->enc_slots < grid) {
+        if (c->enc_scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->enc_scratch); c->enc_scratch = nullptr; c->enc_slots = 0; }
+        CZ_HIP(c, hipMalloc((void**)&c->enc_scratch, (size_t)grid * CZE_SCRATCH_BYTES));
+        c->enc_slots = grid;
+    }
+    if (!c->enc_counter) CZ_HIP(c, hipMalloc((void**)&c->enc_counter, 64));
+    CZ_HIP(c, hipMemsetAsync(c->enc_counter, 0, 4, c->stream));
+    cz_enc_args a; memset(&a, 0, sizeof a);
+    a.in_base = (const uint8_t*)d_in_base; a.in_off = d_in_off; a.in_len = d_in_len;
+    a.out_base = (uint8_t*)d_out_base; a.out_off = d_out_off; a.out_cap = d_out_cap; a.results = d_results;
+    a.n = (uint32_t)n; a.flags = flags; a.work_counter = c->enc_counter; a.scratch = c->enc_scratch; a.scratch_stride = CZE_SCRATCH_BYTES;
+    hipLaunchKernelGGL(cz_compress_frames_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, a);
+    CZ_HIP(c, hipGetLastError());
+    c->last_grid = grid;
+    return CZ_OK;
+}
+
+CZ_EXPORT int cz_compress_batch_host(cz_context* c, const void* in_base, size_t in_bytes, const uint64_t* in_off, const uint64_t* in_len, size_t n,
+                                     void* out_base, size_t out_bytes, const uint64_t* out_off, const uint64_t* out_cap, uint32_t flags,
+                                     cz_compress_result* results) {
+    if (!c || (flags & ~CZ_COMPRESS_CHECKSUM)) return CZ_E_INVALID_ARG;
+    if (n == 0) return CZ_OK;
+    if (!in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !results) return CZ_E_INVALID_ARG;
+    for (size_t i = 0; i < n; i++) {
+        if (in_off[i] > in_bytes || in_len[i] > in_bytes - in_off[i]) return CZ_E_INVALID_ARG;
+        if (out_off[i] > out_bytes || out_cap[i] > out_bytes - out_off[i]) return CZ_E_INVALID_ARG;
+    }
+    CZ_HIP(c, hipSetDevice(c->device));
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_in = 0, o_out = o_in + up(in_bytes + 16), o_desc = o_out + up(out_bytes + 16), o_res = o_desc + up(4 * n * 8);
+    const size_t total = o_res + up(n * sizeof(cz_compress_result));
+    int st = cz_stage_reserve(c, total); if (st) return st;
+    uint8_t* d = (uint8_t*)c->d_stage;
+    uint64_t* d_desc = (uint64_t*)(d + o_desc);
+    CZ_HIP(c, hipMemcpyAsync(d + o_in, in_base, in_bytes, hipMemcpyHostToDevice, c->stream));
+    CZ_HIP(c, hipMemcpyAsync(d_desc, in_off, n * 8, hipMemcpyHostToDevice, c->stream));
+    CZ_HIP(c, hipMemcpyAsync(d_desc + n, in_len, n * 8, hipMemcpyHostToDevice, c->stream));
+    CZ_HIP(c, hipMemcpyAsync(d_desc + 2 * n, out_off, n * 8, hipMemcpyHostToDevice, c->stream));
+    CZ_HIP(c, hipMemcpyAsync(d_desc + 3 * n, out_cap, n * 8, hipMemcpyHostToDevice, c->stream));
+    /* the caller's output buffer as it is: bytes no frame writes come back unchanged */
+    CZ_HIP(c, hipMemcpyAsync(d + o_out, out_base, out_bytes, hipMemcpyHostToDevice, c->stream));
+    st = cz_compress_batch_device(c, d + o_in, d_desc, d_desc + n, n, d + o_out, d_desc + 2 * n, d_desc + 3 * n, flags, (cz_compress_result*)(d + o_res));
+    if (st) return st;
+    CZ_HIP(c, hipMemcpyAsync(out_base, d + o_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    CZ_HIP(c, hipMemcpyAsync(results, d + o_res, n * sizeof(cz_compress_result), hipMemcpyDeviceToHost, c->stream));
     CZ_HIP(c, hipStreamSynchronize(c->stream));
     return CZ_OK;
 }

@@ -423,6 +423,40 @@ cz_decoder_scratch* cz_frame_decoder_scratch(cz_frame_decoder* fd);
 int  cz_frame_decoder_decode_from_to(cz_frame_decoder* fd, const uint8_t* src, size_t len, uint8_t* dst, size_t cap,
                                      size_t* read_len, size_t* written);
 
+
+/* ------------------------------------------------------------- compression */
+/*
+ * Batched compression: n independent buffers become n standard zstd frames in one launch (cz_compress_frames_kernel,
+ * DESIGN.md §10).  Any conforming decoder reads them.  One level: greedy matches from a hash table of 4-byte keys.
+ * Frame format: magic; Frame_Content_Size always written; Single_Segment when the input is at most 1 MiB, otherwise a
+ * 1 MiB window (no offset exceeds it); no Dictionary_ID.  Blocks of at most 128 KiB, each Raw, RLE or Compressed,
+ * whichever is smallest (an empty input: one empty last Raw block).  Literals Raw, RLE or Huffman (one stream below
+ * 1 KiB of literals, four from 1 KiB, codes of at most 11 bits); sequences with the Predefined tables.  A frame's bytes
+ * depend on its input bytes and `flags` alone, never on the batch it was compressed in.
+ */
+/* Worst-case frame size for src_len bytes: frame header, a Raw block header per 128 KiB and the optional checksum. */
+uint64_t cz_compress_bound(uint64_t src_len);
+#define CZ_COMPRESS_CHECKSUM 1u     /* append the 4-byte XXH64 content checksum (Content_Checksum_flag) */
+/* One per buffer, written by the device. */
+typedef struct cz_compress_result {
+    int32_t  status;            /* CZ_OK | CZ_E_OUTPUT_TOO_SMALL | CZ_E_INVALID_ARG (an input of 4 GiB - 1 MiB or more) */
+    uint32_t blocks;            /* blocks written */
+    uint64_t bytes_read;        /* input bytes compressed into the blocks written */
+    uint64_t bytes_written;     /* frame bytes at out_base + out_off[i]; nothing past them is touched */
+    uint32_t checksum;          /* low 32 bits of XXH64 of the input when flags has CZ_COMPRESS_CHECKSUM */
+    uint32_t flags;             /* the flags the frame was written with */
+} cz_compress_result;
+/* Compresses in_base[in_off[i] .. +in_len[i]) into out_base[out_off[i] .. +out_cap[i]) for every i < n.  DEVICE pointers
+ * (results too); asynchronous on the context stream; no alignment required.  A frame that fails leaves its neighbours and
+ * every byte of its own region past bytes_written untouched.  out_cap[i] = cz_compress_bound(in_len[i]) always suffices. */
+int cz_compress_batch_device(cz_context* ctx, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
+                             void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
+                             cz_compress_result* d_results);
+/* Same with HOST buffers: stages the inputs, compresses, copies outputs and results back, and synchronizes. */
+int cz_compress_batch_host(cz_context* ctx, const void* in_base, size_t in_bytes, const uint64_t* in_off, const uint64_t* in_len, size_t n,
+                           void* out_base, size_t out_bytes, const uint64_t* out_off, const uint64_t* out_cap, uint32_t flags,
+                           cz_compress_result* results);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,121 @@
+"""Throughput and ratio of the batched compressor (cz_compress_batch_device) next to libzstd level 1 on 16 CPU threads.
+
+Run it on the GPU box under a time limit of its own, e.g.
+    timeout -k 10 600 python scripts/compress_bench.py --out profiles/compress/bench.json
+Two batches tiled from the golden corpus originals (tests/golden/decode_corpus): 10 000 x 128 KiB and 64 x 2 MiB.  The device
+figure is input bytes over the kernel time (hipEvents around the launch, median of --runs after one warm-up), buffers already in
+HBM.  libzstd (ZSTD_compress, level 1, dlopen'ed) runs the same buffers on --threads threads; it is skipped when the host has no
+libzstd.so.1.  Prints one JSON line per batch and writes them all to --out."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def corpus_pool():
+    d = os.path.join(ROOT, "tests", "golden", "decode_corpus")
+    return b"".join(open(os.path.join(d, n), "rb").read() for n in sorted(os.listdir(d)) if not n.endswith(".zst"))
+
+
+def tiled(n, size, seed):
+    pool = corpus_pool()
+    pool = pool * (size // len(pool) + 2)
+    starts = np.random.default_rng(seed).integers(0, len(pool) - size, n)
+    return [pool[int(s):int(s) + size] for s in starts]
+
+
+def device_run(cz, ctx, stream, bufs, runs):
+    import torch
+    dev = torch.device("cuda:0")
+    lens = np.array([len(b) for b in bufs], dtype=np.uint64)
+    in_off = np.zeros(len(bufs), dtype=np.uint64)
+    in_off[1:] = np.cumsum(lens[:-1])
+    caps = np.array([cz.compress_bound(int(l)) for l in lens], dtype=np.uint64)
+    out_off = np.zeros(len(bufs), dtype=np.uint64)
+    out_off[1:] = np.cumsum(caps[:-1])
+    d_in = torch.from_numpy(np.frombuffer(b"".join(bufs), dtype=np.uint8).copy()).to(dev)
+    d_out = torch.empty(int(caps.sum()), dtype=torch.uint8, device=dev)
+    desc = torch.from_numpy(np.stack([in_off, lens, out_off, caps]).view(np.int64)).to(dev)
+    d_res = torch.zeros(len(bufs) * 32, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    times = []
+    for r in range(runs + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        ctx.compress_batch_device(d_in.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), len(bufs), d_out.data_ptr(),
+                                  desc[2].data_ptr(), desc[3].data_ptr(), d_res.data_ptr())
+        e1.record(stream)
+        e1.synchronize()
+        if r:
+            times.append(e0.elapsed_time(e1))
+    res = d_res.cpu().numpy().view(cz.COMPRESS_RESULT_DTYPE)
+    assert (res["status"] == 0).all()
+    return float(np.median(times)), int(res["bytes_written"].sum())
+
+
+def libzstd_run(bufs, threads, runs):
+    try:
+        z = ctypes.CDLL("libzstd.so.1")
+    except OSError:
+        return None
+    z.ZSTD_compressBound.restype = ctypes.c_size_t
+    z.ZSTD_compressBound.argtypes = [ctypes.c_size_t]
+    z.ZSTD_compress.restype = ctypes.c_size_t
+    z.ZSTD_compress.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int]
+    z.ZSTD_versionNumber.restype = ctypes.c_uint
+    outs = [ctypes.create_string_buffer(z.ZSTD_compressBound(len(b))) for b in bufs]
+
+    def one(i):
+        return z.ZSTD_compress(outs[i], len(outs[i]), bufs[i], len(bufs[i]), 1)     # ctypes drops the GIL around the call
+    best, total = None, 0
+    with ThreadPoolExecutor(threads) as ex:
+        for _ in range(runs):
+            t = time.perf_counter()
+            sizes = list(ex.map(one, range(len(bufs)), chunksize=max(1, len(bufs) // (threads * 8))))
+            dt = time.perf_counter() - t
+            best = dt if best is None else min(best, dt)
+            total = sum(sizes)
+    return best * 1e3, total, z.ZSTD_versionNumber()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--threads", type=int, default=16)
+    args = ap.parse_args()
+    import torch
+    import cairo_zstd_amd as cz
+    stream = torch.cuda.Stream()                                        # the context launches on it, the events are recorded on it
+    ctx = cz.Context(0, stream.cuda_stream)
+    rows = []
+    for name, n, size in (("10000x128KiB", 10000, 128 << 10), ("64x2MiB", 64, 2 << 20)):
+        bufs = tiled(n, size, seed=1)
+        nbytes = n * size
+        ms, written = device_run(cz, ctx, stream, bufs, args.runs)
+        row = dict(batch=name, input_bytes=nbytes, device=torch.cuda.get_device_name(0), device_ms=round(ms, 3),
+                   device_gbps=round(nbytes / ms / 1e6, 2), device_ratio=round(nbytes / written, 4))
+        cpu = libzstd_run(bufs, args.threads, args.runs)
+        if cpu:
+            cms, cwritten, ver = cpu
+            row.update(libzstd_version=ver, libzstd_level=1, libzstd_threads=args.threads, libzstd_ms=round(cms, 3),
+                       libzstd_gbps=round(nbytes / cms / 1e6, 2), libzstd_ratio=round(nbytes / cwritten, 4))
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    ctx.close()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
