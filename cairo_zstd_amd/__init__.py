@@ -6,6 +6,7 @@ Python here is a thin mirror over the C ABI (include/cairo_zstd_amd.h, libcairo_
   * FrameDecoder            : FrameDecoderTrait call for call (src/frame_decoder.cairo:107-335)
   * read_frame_header / read_block_header : stateless parsers
   * compress / compress_batch_host / Context.compress_batch_device : batched compression on the device
+  * compress_batch_host_dict / Context.compress_batch_dict_device : the same with dictionaries (Context.set_compress_dictionaries)
 All decoding and compression runs in the HIP kernels; nothing here decodes or compresses on the CPU.
 """
 from __future__ import annotations
@@ -16,7 +17,7 @@ import weakref
 import numpy as np
 
 from . import status
-from ._lib import (COMPRESS_CHECKSUM, COMPRESS_RESULT_DTYPE, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
+from ._lib import (COMPRESS_CHECKSUM, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
                    BlockHeader, FrameHeader, build, lib)
 
 DEBUG_CHAIN_CPP_STEP, DEBUG_NO_HUF1, DEBUG_WX_POISON, DEBUG_EXEC_FIRST = 1, 2, 4, 8     # cz_context_set_debug_flags
@@ -25,7 +26,7 @@ from .status import CzError
 __all__ = ["Context", "FrameDecoder", "BlockDecodingStrategy", "decode_batch_host", "read_frame_header",
            "read_block_header", "graph_replay_available", "RESULT_DTYPE", "RESULT_FINISHED", "RESULT_HAS_CHECKSUM", "RESULT_CHECKSUM_COMPUTED",
            "RESULT_CHECKSUM_MATCH", "status", "CzError", "build", "lib", "compress_bound", "compress_batch_host", "compress",
-           "COMPRESS_CHECKSUM", "COMPRESS_RESULT_DTYPE"]
+           "COMPRESS_CHECKSUM", "COMPRESS_RESULT_DTYPE", "compress_batch_host_dict", "COMPRESS_NO_DICT", "COMPRESS_NO_DICT_ID"]
 
 
 def _as_u8(b) -> np.ndarray:
@@ -106,6 +107,16 @@ class Context:
         if st:
             raise CzError(st, "cz_context_set_dictionaries")
         self._dict = (dicts, no_id)                                      # keep them alive while launches use them
+
+    def set_compress_dictionaries(self, dicts):
+        """The dictionaries later compress_batch_dict_* calls pick from by index (cz_context_set_compress_dictionaries); an empty
+        list clears the setting.  Independent of set_dictionary / set_dictionaries."""
+        dicts = list(dicts)
+        arr = (C.c_void_p * max(len(dicts), 1))(*[d._h if d is not None else None for d in dicts])
+        st = lib().cz_context_set_compress_dictionaries(self._h, arr if dicts else None, len(dicts))
+        if st:
+            raise CzError(st, "cz_context_set_compress_dictionaries")
+        self._cdict = dicts                                              # keep them alive while launches use them
 
     def last_chain_ms(self) -> float:
         """Milliseconds of the last launch spent in the FSE-chain pre-pass kernel (0 when it is off)."""
@@ -281,6 +292,38 @@ class Context:
             raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
         return res
 
+    def compress_batch_dict_device(self, in_base: int, in_off: int, in_len: int, n: int, out_base: int, out_off: int,
+                                   out_cap: int, dict_index: int, results: int, checksum: bool = False, dict_id: bool = True):
+        """cz_compress_batch_dict_device: as compress_batch_device, frame i with dictionary dict_index[i] of
+        set_compress_dictionaries (COMPRESS_NO_DICT: none).  dict_index is a DEVICE pointer to n uint32 (0: every frame uses the
+        one dictionary set).  dict_id=False omits the Dictionary_ID field."""
+        flags = (COMPRESS_CHECKSUM if checksum else 0) | (0 if dict_id else COMPRESS_NO_DICT_ID)
+        st = lib().cz_compress_batch_dict_device(self._h, in_base, in_off, in_len, n, out_base, out_off, out_cap, flags,
+                                                 dict_index or None, results)
+        if st:
+            raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
+
+    def compress_batch_dict_host(self, in_base, in_off, in_len, out_off, out_cap, out: np.ndarray, dict_index,
+                                 checksum: bool = False, dict_id: bool = True):
+        """cz_compress_batch_dict_host: as compress_batch_host, with a dictionary index per buffer (None: every buffer uses the
+        one dictionary set).  Returns the result records."""
+        in_base = _as_u8(in_base)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        in_len = np.ascontiguousarray(in_len, dtype=np.uint64)
+        out_off = np.ascontiguousarray(out_off, dtype=np.uint64)
+        out_cap = np.ascontiguousarray(out_cap, dtype=np.uint64)
+        idx = None if dict_index is None else np.ascontiguousarray(dict_index, dtype=np.uint32)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"]
+        n = int(in_off.size)
+        res = np.zeros(n, dtype=COMPRESS_RESULT_DTYPE)
+        flags = (COMPRESS_CHECKSUM if checksum else 0) | (0 if dict_id else COMPRESS_NO_DICT_ID)
+        st = lib().cz_compress_batch_dict_host(self._h, in_base.ctypes.data if in_base.size else None, in_base.size, in_off.ctypes.data,
+                                               in_len.ctypes.data, n, out.ctypes.data, out.size, out_off.ctypes.data, out_cap.ctypes.data,
+                                               flags, None if idx is None else idx.ctypes.data, res.ctypes.data)
+        if st:
+            raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
+        return res
+
 
 def compress_bound(n: int) -> int:
     """cz_compress_bound: the largest frame cz_compress_batch_* writes for n input bytes."""
@@ -300,6 +343,23 @@ def compress_batch_host(buffers, ctx: Context, checksum: bool = False):
         out_off[1:] = np.cumsum(caps[:-1])
     out = np.zeros(max(int(caps.sum()), 1), dtype=np.uint8)
     res = ctx.compress_batch_host(in_base, in_off, lens, out_off, caps, out, checksum=checksum)
+    return [(res[i], out[int(out_off[i]): int(out_off[i]) + int(res[i]["bytes_written"])].tobytes()) for i in range(len(buffers))]
+
+
+def compress_batch_host_dict(buffers, dict_index, ctx: Context, checksum: bool = False, dict_id: bool = True):
+    """As compress_batch_host, buffer i with dictionary dict_index[i] of ctx.set_compress_dictionaries (COMPRESS_NO_DICT: none;
+    dict_index None: every buffer uses the one dictionary set): list of (result record, frame bytes)."""
+    lens = np.array([len(b) for b in buffers], dtype=np.uint64)
+    in_off = np.zeros(len(buffers), dtype=np.uint64)
+    if len(buffers) > 1:
+        in_off[1:] = np.cumsum(lens[:-1])
+    in_base = np.frombuffer(b"".join(bytes(b) for b in buffers) + b"\0" * 16, dtype=np.uint8)
+    caps = np.array([compress_bound(int(n)) for n in lens], dtype=np.uint64)
+    out_off = np.zeros(len(buffers), dtype=np.uint64)
+    if len(buffers) > 1:
+        out_off[1:] = np.cumsum(caps[:-1])
+    out = np.zeros(max(int(caps.sum()), 1), dtype=np.uint8)
+    res = ctx.compress_batch_dict_host(in_base, in_off, lens, out_off, caps, out, dict_index, checksum=checksum, dict_id=dict_id)
     return [(res[i], out[int(out_off[i]): int(out_off[i]) + int(res[i]["bytes_written"])].tobytes()) for i in range(len(buffers))]
 
 

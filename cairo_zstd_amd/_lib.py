@@ -23,6 +23,8 @@ COMPRESS_RESULT_DTYPE = np.dtype([("status", "<i4"), ("blocks", "<u4"), ("bytes_
                                   ("checksum", "<u4"), ("flags", "<u4")])
 assert COMPRESS_RESULT_DTYPE.itemsize == 32
 COMPRESS_CHECKSUM = 1
+COMPRESS_NO_DICT_ID = 2                 # omit the Dictionary_ID field (cz_compress_batch_dict_*)
+COMPRESS_NO_DICT = 0xFFFFFFFF           # dict_index entry: no dictionary for this buffer
 
 
 class FrameHeader(C.Structure):
@@ -148,6 +150,12 @@ def lib() -> C.CDLL:
     L.cz_compress_batch_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, C.c_uint32, vp]
     L.cz_compress_batch_host.restype = C.c_int
     L.cz_compress_batch_host.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, C.c_uint32, vp]
+    L.cz_context_set_compress_dictionaries.restype = C.c_int
+    L.cz_context_set_compress_dictionaries.argtypes = [vp, vp, sz]
+    L.cz_compress_batch_dict_device.restype = C.c_int
+    L.cz_compress_batch_dict_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, C.c_uint32, vp, vp]
+    L.cz_compress_batch_dict_host.restype = C.c_int
+    L.cz_compress_batch_dict_host.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, C.c_uint32, vp, vp]
     L.cz_partition_balanced.restype = C.c_int
     L.cz_partition_balanced.argtypes = [vp, sz, sz, vp]
     L.cz_decode_batch_multi.restype = C.c_int

@@ -17,6 +17,10 @@
  *     all threads  Raw, RLE or Compressed, whichever is smallest, copied to the output
  * The frame bytes depend only on the input bytes and the flags.
  *
+ * cz_compress_frames_dict_kernel (cz_compress_batch_dict_*) writes the same frames against a dictionary that
+ * cz_enc_dict_prep_kernel prepared once: Dictionary_ID in the header, matches into the content, the dictionary's repeat offsets,
+ * Treeless literals and Repeat-mode sequence tables while the frame has not replaced them.
+ *
  * Written so that the CPU SIMT emulator of tests/emu (hip/hip_runtime.h) builds it unchanged.  Needs czstd_kernels.hip first
  * (XXH64 rounds, the LL / ML code tables and the Predefined distributions).
  */
@@ -75,9 +79,51 @@ struct CzeShared {
 };
 __shared__ CzeShared cze;
 
+/* A dictionary prepared for compression (cz_enc_dict_prep_kernel, once per dictionary), in HBM:
+ *   htab    the frame's first hash table: entry h = 1 + the highest content position v with v + 4 <= D, D - v <= 1 MiB and
+ *           hash(content[v..v+4)) = h; 0 when there is none
+ *   hlen / hcode  the dictionary's Huffman code per symbol (length 0: the symbol has no code)
+ *   LL / OF / ML (index 0 / 1 / 2, the decoder's order) FSE encode tables in the compact form: fstate[cumul[s] + rank] = the
+ *           decoder state of that rank of symbol s; per symbol deltaFindState (cumul[s] - count), deltaNbBits and the state a
+ *           stream may start in (0xFFFF: the table has no state for the symbol) */
+struct CzeDict {
+    uint32_t htab[1u << CZE_HASH_LOG];
+    uint16_t hcode[256]; uint8_t hlen[256];
+    uint16_t fstate[3][512];
+    int16_t fdfs[3][64]; uint16_t ffirst[3][64]; uint32_t fdnb[3][64];
+    uint32_t flog[3]; uint32_t pad;
+};
+/* one entry of the table a dictionary batch picks from by index (cz_context_set_compress_dictionaries) */
+struct cze_dict_entry { const CzeDict* img; const uint8_t* content; uint64_t content_len; uint32_t id; uint32_t rep[3]; };
+struct cz_enc_dargs { const cze_dict_entry* dicts; const uint32_t* dict_index; uint32_t ndicts; uint32_t pad; };
+
 __device__ static inline uint32_t cze_hb(uint32_t v) { return 31u - (uint32_t)__clz((int)v); }   /* highest set bit, v > 0 */
 __device__ static inline uint32_t cze_ld4(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 __device__ static inline uint32_t cze_hash(uint32_t key) { return (key * 2654435761u) >> (32 - CZE_HASH_LOG); }
+
+/* Frames with a dictionary see one sequence of virtual positions: content byte v is v, input byte p is D + p. */
+__device__ static inline uint32_t cze_vb(const uint8_t* dct, uint32_t D, const uint8_t* in, uint32_t x) { return x < D ? dct[x] : in[x - D]; }
+__device__ static inline uint32_t cze_vld4(const uint8_t* dct, uint32_t D, const uint8_t* in, uint32_t x) {
+    if (x + 4 <= D) return cze_ld4(dct + x);
+    if (x >= D) return cze_ld4(in + (x - D));
+    uint32_t v = 0;
+    for (uint32_t i = 0; i < 4; i++) v |= cze_vb(dct, D, in, x + i) << (8 * i);
+    return v;
+}
+/* match length at input position p against the virtual position c < D: measured against the content, across its end into the
+   input; 0 when the first 4 bytes differ, at most CZE_CAP */
+__device__ static uint32_t cze_dmatch(const uint8_t* dct, uint32_t D, const uint8_t* in, uint32_t p, uint32_t c, uint32_t lim) {
+    if (cze_ld4(in + p) != cze_vld4(dct, D, in, c)) return 0;
+    uint32_t len = 4;
+    const uint32_t cap = lim - p < CZE_CAP ? lim - p : CZE_CAP;
+    while (len + 4 <= cap) {
+        const uint32_t x = cze_ld4(in + p + len) ^ cze_vld4(dct, D, in, c + len);
+        if (x) return len + ((uint32_t)__builtin_ctz(x) >> 3);
+        len += 4;
+    }
+    while (len < cap && in[p + len] == cze_vb(dct, D, in, c + len)) len++;
+    return len;
+}
 
 /* match length at p against c < p, both in [0, lim): 0 when the first 4 bytes differ, at most CZE_CAP */
 __device__ static uint32_t cze_match(const uint8_t* in, uint32_t p, uint32_t c, uint32_t lim) {
@@ -304,33 +350,63 @@ __device__ static inline uint32_t cze_ml_code(uint32_t ml) {
     while (c < 42 && CZ_ML_BASE[c + 1] <= ml) c++;
     return c;
 }
-/* the sequences section of n sequences (Predefined modes) at out[0, lim); returns its length, or lim + 1 when it does not fit */
-__device__ static uint32_t cze_sequences(const CzeSeq* sq, uint32_t n, uint32_t nlit, uint8_t* out, uint32_t lim) {
-    uint32_t h = 0;
+/* one step of a dictionary FSE table (field f of img) for symbol `code`: from the decoder state s of the symbol after it */
+__device__ static inline uint32_t cze_dfse_step(CzeBits& w, const CzeDict* img, uint32_t f, uint32_t code, uint32_t s) {
+    const uint32_t x = s + (1u << img->flog[f]), nb = (x + img->fdnb[f][code]) >> 16;
+    cze_bits_add(w, x & ((1u << nb) - 1u), nb);
+    return img->fstate[f][(int)(x >> nb) + img->fdfs[f][code]];
+}
+/* the sequences section of n sequences at out[0, lim); returns its length, or lim + 1 when it does not fit.  Predefined modes;
+   with a dictionary (DICT), Repeat for each field of `live` (bit 0 LL, 1 OF, 2 ML: the dictionary's table is still the decoder's)
+   whose dictionary table has a state for every code of the block.  *rep_out: the fields written as Repeat. */
+template <bool DICT>
+__device__ static uint32_t cze_sequences(const CzeSeq* sq, uint32_t n, uint32_t nlit, uint8_t* out, uint32_t lim, const CzeDict* img,
+                                         uint32_t live, uint32_t* rep_out) {
+    uint32_t h = 0, rm = 0;
+    if (DICT) *rep_out = 0;
     if (n < 128) { if (lim < 1) return lim + 1; out[h++] = (uint8_t)n; }
     else if (n < 0x7F00) { if (lim < 2) return lim + 1; out[h++] = (uint8_t)((n >> 8) + 128); out[h++] = (uint8_t)n; }
     else { if (lim < 3) return lim + 1; out[h++] = 0xFF; out[h++] = (uint8_t)(n - 0x7F00); out[h++] = (uint8_t)((n - 0x7F00) >> 8); }
     if (n == 0) return h;
     if (h >= lim) return lim + 1;
-    out[h++] = 0;                                                       /* Predefined LL, OF, ML */
+    if (DICT && live) {
+        rm = live;
+        for (uint32_t k = 0; k < n && rm; k++) {
+            const uint32_t ll = (k + 1 < n ? sq[k + 1].lpos : nlit) - sq[k].lpos;
+            if (img->ffirst[0][cze_ll_code(ll)] == 0xFFFFu) rm &= ~1u;
+            if (img->ffirst[1][cze_hb(sq[k].off)] == 0xFFFFu) rm &= ~2u;
+            if (img->ffirst[2][cze_ml_code(sq[k].ml)] == 0xFFFFu) rm &= ~4u;
+        }
+        *rep_out = rm;
+    }
+    out[h++] = (uint8_t)((rm & 1u ? 3u << 6 : 0u) | (rm & 2u ? 3u << 4 : 0u) | (rm & 4u ? 3u << 2 : 0u));   /* Predefined or Repeat */
     CzeBits w; w.acc = 0; w.nb = 0; w.out = out + h; w.pos = 0; w.lim = lim - h; w.over = 0;
     uint32_t sLL = 0, sML = 0, sOF = 0;
     for (int k = (int)n - 1; k >= 0; k--) {
         const CzeSeq q = sq[k];
         const uint32_t ll = (k + 1 < (int)n ? sq[k + 1].lpos : nlit) - q.lpos;
         const uint32_t llc = cze_ll_code(ll), mlc = cze_ml_code(q.ml), ofc = cze_hb(q.off);
-        if (k == (int)n - 1) { sLL = cze.first_ll[llc]; sML = cze.first_ml[mlc]; sOF = cze.first_of[ofc]; }
-        else {
-            uint32_t u = cze.enc_of[ofc * 32 + sOF]; cze_bits_add(w, sOF - cze.base_of[u], cze.nb_of[u]); sOF = u;
-            u = cze.enc_ml[mlc * 64 + sML]; cze_bits_add(w, sML - cze.base_ml[u], cze.nb_ml[u]); sML = u;
-            u = cze.enc_ll[llc * 64 + sLL]; cze_bits_add(w, sLL - cze.base_ll[u], cze.nb_ll[u]); sLL = u;
+        if (k == (int)n - 1) {
+            sLL = DICT && (rm & 1u) ? img->ffirst[0][llc] : cze.first_ll[llc];
+            sML = DICT && (rm & 4u) ? img->ffirst[2][mlc] : cze.first_ml[mlc];
+            sOF = DICT && (rm & 2u) ? img->ffirst[1][ofc] : cze.first_of[ofc];
+        } else {
+            uint32_t u;
+            if (DICT && (rm & 2u)) sOF = cze_dfse_step(w, img, 1, ofc, sOF);
+            else { u = cze.enc_of[ofc * 32 + sOF]; cze_bits_add(w, sOF - cze.base_of[u], cze.nb_of[u]); sOF = u; }
+            if (DICT && (rm & 4u)) sML = cze_dfse_step(w, img, 2, mlc, sML);
+            else { u = cze.enc_ml[mlc * 64 + sML]; cze_bits_add(w, sML - cze.base_ml[u], cze.nb_ml[u]); sML = u; }
+            if (DICT && (rm & 1u)) sLL = cze_dfse_step(w, img, 0, llc, sLL);
+            else { u = cze.enc_ll[llc * 64 + sLL]; cze_bits_add(w, sLL - cze.base_ll[u], cze.nb_ll[u]); sLL = u; }
         }
         cze_bits_add(w, ll - CZ_LL_BASE[llc], CZ_LL_BITS[llc]);
         cze_bits_add(w, q.ml - CZ_ML_BASE[mlc], CZ_ML_BITS[mlc]);
         cze_bits_add(w, q.off - (1u << ofc), ofc);
         if (w.over) return lim + 1;
     }
-    cze_bits_add(w, sML, 6); cze_bits_add(w, sOF, 5); cze_bits_add(w, sLL, 6);
+    cze_bits_add(w, sML, DICT && (rm & 4u) ? img->flog[2] : 6u);
+    cze_bits_add(w, sOF, DICT && (rm & 2u) ? img->flog[1] : 5u);
+    cze_bits_add(w, sLL, DICT && (rm & 1u) ? img->flog[0] : 6u);
     const uint32_t len = cze_bits_close(w);
     return w.over ? lim + 1 : h + len;
 }
@@ -358,8 +434,12 @@ __device__ static uint64_t cze_xxh64(const uint8_t* p, uint64_t len) {
 }
 
 /* ------------------------------------------------------------------ one block */
-/* literals section of lit[0, nlit) at out (room: lim); returns its length; Raw, RLE or Huffman (1 stream below 1 KiB, else 4) */
-__device__ static uint32_t cze_literals(const uint8_t* lit, uint32_t nlit, uint8_t* out, uint32_t* hufw) {
+/* literals section of lit[0, nlit) at out (room: lim); returns its length; Raw, RLE or Huffman (1 stream below 1 KiB, else 4).
+   With a dictionary (DICT) whose Huffman code is still the decoder's table (huf_live), Treeless with that code when every symbol
+   of the block has a code and the section comes out smaller.  *ltype: the Literals_Block_Type written (DICT only). */
+template <bool DICT>
+__device__ static uint32_t cze_literals(const uint8_t* lit, uint32_t nlit, uint8_t* out, uint32_t* hufw, const CzeDict* img, uint32_t huf_live,
+                                        uint32_t* ltype) {
     const uint32_t t = threadIdx.x;
     for (uint32_t s = t; s < 256; s += CZE_THREADS) cze.hist[s] = 0;
     __syncthreads();
@@ -380,6 +460,7 @@ __device__ static uint32_t cze_literals(const uint8_t* lit, uint32_t nlit, uint8
             out[raw_hdr] = lit[0];
         }
         __syncthreads();
+        if (DICT) *ltype = 1;
         return raw_hdr + 1;
     }
     uint32_t huf_len = 0xFFFFFFFFu;
@@ -398,6 +479,7 @@ __device__ static uint32_t cze_literals(const uint8_t* lit, uint32_t nlit, uint8
             const uint32_t hdr = !four ? 3u : (nlit < 16384 && body < 16384 ? 4u : 5u);
             if (hdr + body < raw_hdr + nlit && body < (1u << 18)) {
                 huf_len = hdr + body;
+                if (DICT) *ltype = 2;
                 if (t == 0) {
                     const uint32_t sf = !four ? 0u : (hdr == 4 ? 2u : 3u);
                     const uint32_t bits = hdr == 3 ? 10u : (hdr == 4 ? 14u : 18u);
@@ -423,8 +505,46 @@ __device__ static uint32_t cze_literals(const uint8_t* lit, uint32_t nlit, uint8
         }
         for (uint32_t i = t; i < nlit; i += CZE_THREADS) out[raw_hdr + i] = lit[i];
         huf_len = raw_hdr + nlit;
+        if (DICT) *ltype = 0;
     }
     __syncthreads();
+    if (DICT && huf_live && nlit > 0) {
+        /* Treeless: the exact size from the code lengths, per stream; any symbol without a code rules it out */
+        const uint32_t four = nlit >= 1024, ns = four ? 4u : 1u, seg = four ? (nlit + 3) / 4 : nlit;
+        uint32_t miss = 0, acc[4] = {0, 0, 0, 0};
+        if (t < 256 && cze.hist[t] && !img->hlen[t]) miss = 1;
+        for (uint32_t k = t; k < nlit; k += CZE_THREADS) acc[k / seg] += img->hlen[lit[k]];
+        uint32_t nmiss, bits[4] = {0, 0, 0, 0}, sum = 0;
+        (void)cze_wg_scan(miss, &nmiss);
+        for (uint32_t k = 0; k < ns; k++) { (void)cze_wg_scan(acc[k], &bits[k]); sum += (bits[k] >> 3) + 1; }
+        const uint32_t body = (four ? 6u : 0u) + sum;
+        const uint32_t hdr = !four ? 3u : (nlit < 16384 && body < 16384 ? 4u : 5u);
+        if (!nmiss && hdr + body < huf_len && body < (1u << 18)) {
+            for (uint32_t s = t; s < 256; s += CZE_THREADS) { cze.hlen[s] = img->hlen[s]; cze.hcode[s] = img->hcode[s]; }
+            __syncthreads();
+            uint32_t sb[4] = {0, 0, 0, 0};
+            for (uint32_t k = 0; k < ns; k++) {
+                const uint32_t s0 = k * seg, s1 = (k + 1) * seg < nlit ? (k + 1) * seg : nlit;
+                sb[k] = cze_huf_stream(lit, s0, s1, hufw + k * CZE_HUF_REGION_WORDS);
+            }
+            if (t == 0) {
+                const uint32_t sf = !four ? 0u : (hdr == 4 ? 2u : 3u);
+                const uint32_t nbits = hdr == 3 ? 10u : (hdr == 4 ? 14u : 18u);
+                uint64_t v = 3u | (sf << 2) | ((uint64_t)nlit << 4) | ((uint64_t)body << (4 + nbits));
+                for (uint32_t i = 0; i < hdr; i++) out[i] = (uint8_t)(v >> (8 * i));
+                if (four) for (uint32_t k = 0; k < 3; k++) { out[hdr + 2 * k] = (uint8_t)sb[k]; out[hdr + 2 * k + 1] = (uint8_t)(sb[k] >> 8); }
+            }
+            uint32_t at = hdr + (four ? 6u : 0u);
+            for (uint32_t k = 0; k < ns; k++) {
+                const uint8_t* src = (const uint8_t*)(hufw + k * CZE_HUF_REGION_WORDS);
+                for (uint32_t i = t; i < sb[k]; i += CZE_THREADS) out[at + i] = src[i];
+                at += sb[k];
+            }
+            huf_len = hdr + body;
+            *ltype = 3;
+            __syncthreads();
+        }
+    }
     return huf_len;
 }
 
@@ -561,9 +681,9 @@ __global__ void __launch_bounds__(CZE_THREADS) cz_compress_frames_kernel(cz_enc_
                     cze.rep[0] = h0; cze.rep[1] = h1; cze.rep[2] = h2;
                 }
                 __syncthreads();
-                const uint32_t lsz = cze_literals(lit, nlit, blk, hufw);
+                const uint32_t lsz = cze_literals<false>(lit, nlit, blk, hufw, nullptr, 0u, nullptr);
                 if (lsz < bsize) {
-                    if (t == 0) cze.csize = lsz + cze_sequences(seqs, nseq, nsl, blk + lsz, bsize - lsz);
+                    if (t == 0) cze.csize = lsz + cze_sequences<false>(seqs, nseq, nsl, blk + lsz, bsize - lsz, nullptr, 0u, nullptr);
                     __syncthreads();
                     csize = cze.csize;
                     if (csize < bsize) btype = 2;
@@ -595,5 +715,247 @@ __global__ void __launch_bounds__(CZE_THREADS) cz_compress_frames_kernel(cz_enc_
             res->status = status; res->blocks = nblocks; res->bytes_read = done; res->bytes_written = pos;
             res->checksum = sum; res->flags = flags;
         }
+    }
+}
+
+/* ------------------------------------------------------------------ the kernels */
+/* The body of cz_compress_frames_dict_kernel: frame i starts from dictionary d.dicts[d.dict_index[i]] or, for
+   CZ_COMPRESS_NO_DICT, from nothing, and then comes out exactly as cz_compress_frames_kernel writes it.  With DICT = false it is
+   that kernel's code; the plain kernel keeps its own copy above all the same, because inlining this body into it changed its
+   resources (the compiler promoted the header array to LDS: 3.5 KB more, 9 more SGPR spills). */
+template <bool DICT>
+__device__ static __forceinline__ void cze_frames(cz_enc_args a, cz_enc_dargs d) {
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    /* Predefined tables (RFC 8878 §3.1.1.3.2.2): spread by lanes 0..2, then one thread per state */
+    if (t < 3) {
+        if (t == 0) cze_fse_spread(CZ_LL_DEFAULT, 36, 6, cze.sym_tmp[0]);
+        else if (t == 1) cze_fse_spread(CZ_ML_DEFAULT, 53, 6, cze.sym_tmp[1]);
+        else cze_fse_spread(CZ_OF_DEFAULT, 29, 5, cze.sym_tmp[2]);
+    }
+    __syncthreads();
+    if (t < 64) cze_fse_state(CZ_LL_DEFAULT, cze.sym_tmp[0], 6, t, cze.nb_ll, cze.base_ll, cze.enc_ll, cze.first_ll);
+    else if (t < 128) cze_fse_state(CZ_ML_DEFAULT, cze.sym_tmp[1], 6, t - 64, cze.nb_ml, cze.base_ml, cze.enc_ml, cze.first_ml);
+    else if (t < 160) cze_fse_state(CZ_OF_DEFAULT, cze.sym_tmp[2], 5, t - 128, cze.nb_of, cze.base_of, cze.enc_of, cze.first_of);
+    uint8_t* scr = a.scratch + (uint64_t)blockIdx.x * a.scratch_stride;
+    uint8_t* lit = scr + CZE_SCR_LIT;
+    CzeSeq* seqs = (CzeSeq*)(scr + CZE_SCR_SEQ);
+    uint32_t* hufw = (uint32_t*)(scr + CZE_SCR_HUF);
+    uint8_t* blk = scr + CZE_SCR_BLK;
+    for (;;) {
+        __syncthreads();
+        if (t == 0) cze.frame = atomicAdd(a.work_counter, 1u);
+        __syncthreads();
+        const uint32_t f = cze.frame;
+        if (f >= a.n) break;
+        const uint8_t* in = a.in_base + a.in_off[f];
+        const uint64_t len64 = a.in_len[f];
+        uint8_t* out = a.out_base + a.out_off[f];
+        const uint64_t cap = a.out_cap[f];
+        cz_compress_result* res = a.results + f;
+        const uint32_t flags = a.flags & CZ_COMPRESS_CHECKSUM;
+        const CzeDict* img = nullptr; const uint8_t* dct = nullptr; uint64_t dlen = 0; uint32_t did = 0, bad_index = 0;
+        if (DICT) {
+            const uint32_t di = d.dict_index ? d.dict_index[f] : 0u;
+            if (di != CZ_COMPRESS_NO_DICT) {
+                if (di >= d.ndicts) bad_index = 1;
+                else { const cze_dict_entry& e = d.dicts[di]; img = e.img; dct = e.content; dlen = e.content_len; did = e.id; }
+            }
+        }
+        if (len64 + dlen >= 0xFFF00000ull || bad_index) {               /* (virtual) positions are 32-bit */
+            if (t == 0) { res->status = CZ_E_INVALID_ARG; res->blocks = 0; res->bytes_read = 0; res->bytes_written = 0; res->checksum = 0; res->flags = flags; }
+            continue;
+        }
+        const uint32_t len = (uint32_t)len64, D = DICT ? (uint32_t)dlen : 0u;
+        if (DICT && img) {                                              /* the table starts as the dictionary's */
+            for (uint32_t k = t; k < (1u << CZE_HASH_LOG) / 4u; k += CZE_THREADS) {
+                const uint4 v = ((const uint4*)img->htab)[k];
+                cze.htab[4 * k] = v.x; cze.htab[4 * k + 1] = v.y; cze.htab[4 * k + 2] = v.z; cze.htab[4 * k + 3] = v.w;
+            }
+            if (t == 0) { const cze_dict_entry& e = d.dicts[d.dict_index ? d.dict_index[f] : 0u]; cze.rep[0] = e.rep[0]; cze.rep[1] = e.rep[1]; cze.rep[2] = e.rep[2]; }
+        } else {
+            for (uint32_t k = t; k < (1u << CZE_HASH_LOG); k += CZE_THREADS) cze.htab[k] = 0;
+            if (t == 0) { cze.rep[0] = 1; cze.rep[1] = 4; cze.rep[2] = 8; }
+        }
+        /* which of the dictionary's tables are still the decoder's: its Huffman table (every thread), its LL / OF / ML tables
+           (bits 0..2; lane 0 writes the sequences) */
+        uint32_t huf_live = DICT && img, fse_live = DICT && img ? 7u : 0u;
+        /* frame header */
+        const uint32_t single = len <= (1u << 20);
+        uint8_t hdr[14]; uint32_t hl = 0;
+        hdr[hl++] = 0x28; hdr[hl++] = 0xB5; hdr[hl++] = 0x2F; hdr[hl++] = 0xFD;
+        const uint32_t fcs_flag = single && len < 256 ? 0u : (len >= 256 && len < 65536 + 256 ? 1u : 2u);
+        const uint32_t idb = !DICT || !img || did == 0 || (a.flags & CZ_COMPRESS_NO_DICT_ID) ? 0u : (did < 256 ? 1u : (did < 65536 ? 2u : 4u));
+        hdr[hl++] = (uint8_t)((fcs_flag << 6) | (single << 5) | (flags ? 4u : 0u) | (idb == 4 ? 3u : idb));
+        if (!single) hdr[hl++] = (uint8_t)((20 - 10) << 3);            /* Window_Descriptor: 1 MiB */
+        for (uint32_t i = 0; i < idb; i++) hdr[hl++] = (uint8_t)(did >> (8 * i));   /* Dictionary_ID: the smallest field that holds it */
+        if (fcs_flag == 0) hdr[hl++] = (uint8_t)len;
+        else if (fcs_flag == 1) { hdr[hl++] = (uint8_t)(len - 256); hdr[hl++] = (uint8_t)((len - 256) >> 8); }
+        else for (int i = 0; i < 4; i++) hdr[hl++] = (uint8_t)(len >> (8 * i));
+        int status = CZ_OK; uint64_t pos = 0; uint32_t nblocks = 0, done = 0;
+        if (hl <= cap) { for (uint32_t i = t; i < hl; i += CZE_THREADS) out[i] = hdr[i]; pos = hl; }
+        else status = CZ_E_OUTPUT_TOO_SMALL;
+        for (uint32_t b0 = 0; status == CZ_OK && (b0 < len || (len == 0 && nblocks == 0));) {
+            const uint32_t bsize = len - b0 < CZE_BLOCK ? len - b0 : CZE_BLOCK, b1 = b0 + bsize, last = b1 == len;
+            /* RLE block? */
+            if (t == 0) cze.rle = bsize > 0;
+            __syncthreads();
+            for (uint32_t k = t; k < bsize; k += CZE_THREADS) if (in[b0 + k] != in[b0]) cze.rle = 0;
+            __syncthreads();
+            const uint32_t rle = cze.rle;
+            uint32_t btype = 0, csize = 0;                              /* 0 Raw, 1 RLE, 2 Compressed */
+            if (rle) btype = 1;
+            else if (bsize >= 16) {
+                /* matches, chunk by chunk; wave 0 parses each chunk behind the parallel pass */
+                uint32_t pp = b0, lit_start = b0, nseq = 0, nlit = 0;
+                for (uint32_t c0 = b0; c0 < b1; c0 += CZE_CHUNK) {
+                    const uint32_t p = c0 + t, valid = p + 4 <= b1;
+                    const uint32_t h = valid ? cze_hash(cze_ld4(in + p)) : 0xFFFFFFFFu;
+                    cze.chash[t] = h;
+                    const uint32_t old = valid ? cze.htab[h] : 0;     /* (virtual) position + 1 */
+                    __syncthreads();
+                    uint32_t mlen = 0, moff = 0;
+                    if (valid) {
+                        const uint32_t lo = t > CZE_BACK ? t - CZE_BACK : 0;
+                        for (int j = (int)t - 1; j >= (int)lo; j--) if (cze.chash[j] == h) {
+                            const uint32_t m = cze_match(in, p, c0 + (uint32_t)j, b1);
+                            if (m >= 4) { mlen = m; moff = t - (uint32_t)j; }
+                            break;
+                        }
+                        if (!mlen && old && D + p - (old - 1) <= CZE_WINDOW) {
+                            const uint32_t c = old - 1;
+                            const uint32_t m = DICT && c < D ? cze_dmatch(dct, D, in, p, c, b1) : cze_match(in, p, c - D, b1);
+                            if (m >= 4) { mlen = m; moff = D + p - c; }
+                        }
+                        atomicMax(&cze.htab[h], D + p + 1);
+                    }
+                    cze.cmlen[t] = (uint16_t)mlen; cze.cmoff[t] = moff;
+                    __syncthreads();
+                    if (wave == 0) {
+                        const uint32_t cend = c0 + CZE_CHUNK < b1 ? c0 + CZE_CHUNK : b1;
+                        while (pp < cend) {
+                            const uint32_t q = pp + lane;
+                            const uint64_t mask = __ballot(q < cend && cze.cmlen[q - c0] >= 4);
+                            if (!mask) { pp = pp + 64 < cend ? pp + 64 : cend; continue; }
+                            pp += (uint32_t)__ffsll((long long)mask) - 1;
+                            uint32_t ml = cze.cmlen[pp - c0];
+                            const uint32_t off = cze.cmoff[pp - c0];
+                            if (ml >= CZE_CAP) {
+                                for (;;) {
+                                    const uint32_t r = pp + ml + lane;
+                                    const uint64_t bad = __ballot(r >= b1 || in[r] != (DICT ? cze_vb(dct, D, in, D + r - off) : in[r - off]));
+                                    if (!bad) { ml += 64; continue; }
+                                    ml += (uint32_t)__ffsll((long long)bad) - 1;
+                                    break;
+                                }
+                            }
+                            if (lane == 0) { CzeSeq s; s.mstart = pp - b0; s.ml = ml; s.off = off; s.lpos = nlit; seqs[nseq] = s; }
+                            nlit += pp - lit_start; nseq++;
+                            pp += ml; lit_start = pp;
+                        }
+                    }
+                }
+                if (t == 0) { cze.nseq = nseq; cze.nseqlit = nlit; cze.nlit = nlit + (b1 - lit_start); }
+                __syncthreads();
+                nseq = cze.nseq; nlit = cze.nlit;
+                const uint32_t nsl = cze.nseqlit;                       /* literals of the sequences; the rest trail the last one */
+                /* gather the literals: a wave per sequence, then the tail */
+                for (uint32_t s = wave; s <= nseq; s += CZE_WAVES) {
+                    uint32_t src, dst, n;
+                    if (s < nseq) { const CzeSeq q = seqs[s]; dst = q.lpos; n = (s + 1 < nseq ? seqs[s + 1].lpos : nsl) - dst; src = b0 + q.mstart - n; }
+                    else { dst = nsl; n = nlit - nsl; src = b1 - n; }
+                    for (uint32_t k = lane; k < n; k += 64) lit[dst + k] = in[src + k];
+                }
+                __syncthreads();
+                /* repeat offsets, forward (only the case Offset_Value 1 with literals: the history then stays) */
+                const uint32_t r0 = cze.rep[0], r1 = cze.rep[1], r2 = cze.rep[2];
+                if (t == 0) {
+                    uint32_t h0 = r0, h1 = r1, h2 = r2;
+                    for (uint32_t s = 0; s < nseq; s++) {
+                        const uint32_t ll = (s + 1 < nseq ? seqs[s + 1].lpos : nsl) - seqs[s].lpos, off = seqs[s].off;
+                        if (ll > 0 && off == h0) seqs[s].off = 1;
+                        else { seqs[s].off = off + 3; h2 = h1; h1 = h0; h0 = off; }
+                    }
+                    cze.rep[0] = h0; cze.rep[1] = h1; cze.rep[2] = h2;
+                }
+                __syncthreads();
+                uint32_t ltype = 0, srep = 0;
+                const uint32_t lsz = cze_literals<DICT>(lit, nlit, blk, hufw, img, huf_live, &ltype);
+                if (lsz < bsize) {
+                    if (t == 0) cze.csize = lsz + cze_sequences<DICT>(seqs, nseq, nsl, blk + lsz, bsize - lsz, img, fse_live, &srep);
+                    __syncthreads();
+                    csize = cze.csize;
+                    if (csize < bsize) btype = 2;
+                }
+                if (btype != 2) {                                       /* the decoder will not see these sequences */
+                    __syncthreads();
+                    if (t == 0) { cze.rep[0] = r0; cze.rep[1] = r1; cze.rep[2] = r2; }
+                } else if (DICT) {                                      /* ... and only a Compressed block changes its tables */
+                    if (ltype == 2) huf_live = 0;
+                    if (nseq) fse_live &= srep;
+                }
+            }
+            const uint32_t body = btype == 0 ? bsize : (btype == 1 ? 1u : csize);
+            if (pos + 3 + body > cap) { status = CZ_E_OUTPUT_TOO_SMALL; break; }
+            const uint32_t bh = last | (btype << 1) | ((btype == 2 ? csize : bsize) << 3);
+            if (t == 0) { out[pos] = (uint8_t)bh; out[pos + 1] = (uint8_t)(bh >> 8); out[pos + 2] = (uint8_t)(bh >> 16); }
+            const uint8_t* src = btype == 0 ? in + b0 : (btype == 1 ? in + b0 : blk);
+            for (uint32_t i = t; i < body; i += CZE_THREADS) out[pos + 3 + i] = src[i];
+            pos += 3 + body; nblocks++; done = b1;
+            b0 = b1;
+            __syncthreads();
+        }
+        uint32_t sum = 0;
+        if (status == CZ_OK && flags) {
+            if (wave == 0) { const uint64_t x = cze_xxh64(in, len); if (t == 0) cze.csize = (uint32_t)x; }
+            __syncthreads();
+            sum = cze.csize;
+            if (pos + 4 > cap) status = CZ_E_OUTPUT_TOO_SMALL;
+            else { if (t < 4) out[pos + t] = (uint8_t)(sum >> (8 * t)); pos += 4; }
+        }
+        if (t == 0) {
+            res->status = status; res->blocks = nblocks; res->bytes_read = done; res->bytes_written = pos;
+            res->checksum = sum; res->flags = flags;
+        }
+    }
+}
+
+/* cz_compress_batch_dict_*: the same frames, each from its dictionary (or none) */
+__global__ void __launch_bounds__(CZE_THREADS) cz_compress_frames_dict_kernel(cz_enc_args a, cz_enc_dargs d) {
+    cze_frames<true>(a, d);
+}
+
+/* Prepares a dictionary for compression (CzeDict, zeroed by the host): every workgroup inserts its share of the content positions
+   into the hash table (atomicMax: the highest position wins whatever the schedule); workgroup 0 also derives the Huffman code
+   from the decoder's table and the compact FSE encode tables from the decoder's LL / OF / ML tables (cz_dict_setup_kernel). */
+__global__ void __launch_bounds__(CZE_THREADS) cz_enc_dict_prep_kernel(const cz_device_frame_state* st, const uint8_t* content, uint64_t D,
+                                                                        CzeDict* img) {
+    const uint32_t t = threadIdx.x;
+    const uint64_t lo = D > CZE_WINDOW ? D - CZE_WINDOW : 0;
+    for (uint64_t v = lo + (uint64_t)blockIdx.x * CZE_THREADS + t; v + 4 <= D; v += (uint64_t)gridDim.x * CZE_THREADS)
+        atomicMax(&img->htab[cze_hash(cze_ld4(content + v))], (uint32_t)v + 1u);
+    if (blockIdx.x != 0) return;
+    /* huf[] holds symbol | length << 8 per cell of 2^max_bits; a symbol's code is the index of its first cell >> (max_bits - length) */
+    const uint32_t mb = st->huf_max_bits;
+    for (uint32_t i = t; mb && i < (1u << mb); i += CZE_THREADS) {
+        const uint32_t e = st->huf[i], s = e & 0xFFu, l = (e >> 8) & 15u;
+        if (l && l <= mb && !(i & ((1u << (mb - l)) - 1u))) { img->hlen[s] = (uint8_t)l; img->hcode[s] = (uint16_t)(i >> (mb - l)); }
+    }
+    if (t < 3) {                                                        /* one lane per table: count, cumulate, rank in state order */
+        const uint32_t log = st->fse_log[t], size = 1u << log;
+        uint32_t cnt[64], cum[64];
+        for (uint32_t s = 0; s < 64; s++) cnt[s] = 0;
+        for (uint32_t u = 0; u < size; u++) cnt[(st->fse[t][u] >> 24) & 63u]++;
+        uint32_t c = 0;
+        for (uint32_t s = 0; s < 64; s++) { cum[s] = c; c += cnt[s]; }
+        for (uint32_t u = 0; u < size; u++) { const uint32_t s = (st->fse[t][u] >> 24) & 63u; img->fstate[t][cum[s]++] = (uint16_t)u; }
+        for (uint32_t s = 0; s < 64; s++) {
+            const uint32_t n = cnt[s], c0 = cum[s] - n;
+            if (!n) { img->ffirst[t][s] = 0xFFFFu; img->fdfs[t][s] = 0; img->fdnb[t][s] = 0; continue; }
+            const uint32_t mbo = n == 1 ? log : log - cze_hb(n - 1);
+            img->fdfs[t][s] = (int16_t)((int32_t)c0 - (int32_t)n);
+            img->fdnb[t][s] = (mbo << 16) - (n << mbo);
+            img->ffirst[t][s] = img->fstate[t][c0];
+        }
+        img->flog[t] = log;
     }
 }

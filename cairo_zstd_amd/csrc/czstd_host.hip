@@ -73,6 +73,7 @@ struct cz_dictionary {
     uint8_t* d_raw = nullptr; size_t len = 0; size_t content_off = 0;
     cz_device_frame_state* d_state = nullptr;
     uint32_t id = 0; uint32_t hist[3] = {0, 0, 0};
+    CzeDict* d_enc = nullptr;               /* prepared for compression (cz_enc_dict_prep_kernel) by the first cz_context_set_compress_dictionaries */
 };
 struct cz_context {
     int device = 0;
@@ -98,6 +99,7 @@ struct cz_context {
     int last_hip_error = 0, last_hip_line = 0;
     /* batched compression (cz_compress_batch_*): per-workgroup scratch of cz_compress_frames_kernel, allocated by the first call */
     uint8_t* enc_scratch = nullptr; int enc_slots = 0; uint32_t* enc_counter = nullptr; int enc_grid = 0;
+    cze_dict_entry* enc_dicts = nullptr; uint32_t enc_dict_count = 0; int enc_dgrid = 0;   /* cz_context_set_compress_dictionaries */
     /* staging for cz_decode_batch_host */
     void* d_stage = nullptr; size_t d_stage_bytes = 0;
     void* h_pin = nullptr; size_t h_pin_bytes = 0;                      /* pinned host staging of cz_decode_batch_multi's share */
@@ -189,6 +191,7 @@ CZ_EXPORT void cz_context_destroy(cz_context* c) {
     if (c->lit_scratch) (void)hipFree(c->lit_scratch);
     if (c->enc_scratch) (void)hipFree(c->enc_scratch);
     if (c->enc_counter) (void)hipFree(c->enc_counter);
+    if (c->enc_dicts) (void)hipFree(c->enc_dicts);
     if (c->work_counter) (void)hipFree(c->work_counter);
     if (c->d_stage) (void)hipFree(c->d_stage);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
@@ -931,6 +934,18 @@ CZ_EXPORT uint64_t cz_compress_bound(uint64_t src_len) {
     return 14 + 4 + 3 * blocks + src_len;              /* largest frame header, a Raw block header per block, the checksum */
 }
 
+/* scratch and work counter of the compress kernels, sized for `grid` workgroups */
+static int cz_enc_reserve(cz_context* c, int grid) {
+    if (c->enc_slots < grid) {
+        if (c->enc_scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->enc_scratch); c->enc_scratch = nullptr; c->enc_slots = 0; }
+        CZ_HIP(c, hipMalloc((void**)&c->enc_scratch, (size_t)grid * CZE_SCRATCH_BYTES));
+        c->enc_slots = grid;
+    }
+    if (!c->enc_counter) CZ_HIP(c, hipMalloc((void**)&c->enc_counter, 64));
+    CZ_HIP(c, hipMemsetAsync(c->enc_counter, 0, 4, c->stream));
+    return CZ_OK;
+}
+
 CZ_EXPORT int cz_compress_batch_device(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                                        void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                                        cz_compress_result* d_results) {
@@ -944,13 +959,7 @@ CZ_EXPORT int cz_compress_batch_device(cz_context* c, const void* d_in_base, con
         c->enc_grid = c->num_cu * occ;
     }
     const int grid = (size_t)c->enc_grid < n ? c->enc_grid : (int)n;
-    if (c->enc_slots < grid) {
-        if (c->enc_scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->enc_scratch); c->enc_scratch = nullptr; c->enc_slots = 0; }
-        CZ_HIP(c, hipMalloc((void**)&c->enc_scratch, (size_t)grid * CZE_SCRATCH_BYTES));
-        c->enc_slots = grid;
-    }
-    if (!c->enc_counter) CZ_HIP(c, hipMalloc((void**)&c->enc_counter, 64));
-    CZ_HIP(c, hipMemsetAsync(c->enc_counter, 0, 4, c->stream));
+    const int st = cz_enc_reserve(c, grid); if (st) return st;
     cz_enc_args a; memset(&a, 0, sizeof a);
     a.in_base = (const uint8_t*)d_in_base; a.in_off = d_in_off; a.in_len = d_in_len;
     a.out_base = (uint8_t*)d_out_base; a.out_off = d_out_off; a.out_cap = d_out_cap; a.results = d_results;
@@ -961,11 +970,12 @@ CZ_EXPORT int cz_compress_batch_device(cz_context* c, const void* d_in_base, con
     return CZ_OK;
 }
 
-CZ_EXPORT int cz_compress_batch_host(cz_context* c, const void* in_base, size_t in_bytes, const uint64_t* in_off, const uint64_t* in_len, size_t n,
-                                     void* out_base, size_t out_bytes, const uint64_t* out_off, const uint64_t* out_cap, uint32_t flags,
-                                     cz_compress_result* results) {
-    if (!c || (flags & ~CZ_COMPRESS_CHECKSUM)) return CZ_E_INVALID_ARG;
-    if (n == 0) return CZ_OK;
+/* Stages a host batch (inputs, descriptors, the caller's output buffer as it is, optional dict_index) and runs `launch` on the
+   device copies; copies outputs and results back and synchronizes. */
+template <typename F>
+static int cz_compress_staged(cz_context* c, const void* in_base, size_t in_bytes, const uint64_t* in_off, const uint64_t* in_len, size_t n,
+                              void* out_base, size_t out_bytes, const uint64_t* out_off, const uint64_t* out_cap, const uint32_t* dict_index,
+                              cz_compress_result* results, F launch) {
     if (!in_base || !in_off || !in_len || !out_base || !out_off || !out_cap || !results) return CZ_E_INVALID_ARG;
     for (size_t i = 0; i < n; i++) {
         if (in_off[i] > in_bytes || in_len[i] > in_bytes - in_off[i]) return CZ_E_INVALID_ARG;
@@ -974,7 +984,7 @@ CZ_EXPORT int cz_compress_batch_host(cz_context* c, const void* in_base, size_t 
     CZ_HIP(c, hipSetDevice(c->device));
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t o_in = 0, o_out = o_in + up(in_bytes + 16), o_desc = o_out + up(out_bytes + 16), o_res = o_desc + up(4 * n * 8);
-    const size_t total = o_res + up(n * sizeof(cz_compress_result));
+    const size_t o_idx = o_res + up(n * sizeof(cz_compress_result)), total = o_idx + (dict_index ? up(n * 4) : 0);
     int st = cz_stage_reserve(c, total); if (st) return st;
     uint8_t* d = (uint8_t*)c->d_stage;
     uint64_t* d_desc = (uint64_t*)(d + o_desc);
@@ -983,14 +993,104 @@ CZ_EXPORT int cz_compress_batch_host(cz_context* c, const void* in_base, size_t 
     CZ_HIP(c, hipMemcpyAsync(d_desc + n, in_len, n * 8, hipMemcpyHostToDevice, c->stream));
     CZ_HIP(c, hipMemcpyAsync(d_desc + 2 * n, out_off, n * 8, hipMemcpyHostToDevice, c->stream));
     CZ_HIP(c, hipMemcpyAsync(d_desc + 3 * n, out_cap, n * 8, hipMemcpyHostToDevice, c->stream));
+    if (dict_index) CZ_HIP(c, hipMemcpyAsync(d + o_idx, dict_index, n * 4, hipMemcpyHostToDevice, c->stream));
     /* the caller's output buffer as it is: bytes no frame writes come back unchanged */
     CZ_HIP(c, hipMemcpyAsync(d + o_out, out_base, out_bytes, hipMemcpyHostToDevice, c->stream));
-    st = cz_compress_batch_device(c, d + o_in, d_desc, d_desc + n, n, d + o_out, d_desc + 2 * n, d_desc + 3 * n, flags, (cz_compress_result*)(d + o_res));
+    st = launch(d + o_in, d_desc, d_desc + n, d + o_out, d_desc + 2 * n, d_desc + 3 * n, dict_index ? (const uint32_t*)(d + o_idx) : nullptr,
+                (cz_compress_result*)(d + o_res));
     if (st) return st;
     CZ_HIP(c, hipMemcpyAsync(out_base, d + o_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
     CZ_HIP(c, hipMemcpyAsync(results, d + o_res, n * sizeof(cz_compress_result), hipMemcpyDeviceToHost, c->stream));
     CZ_HIP(c, hipStreamSynchronize(c->stream));
     return CZ_OK;
+}
+
+CZ_EXPORT int cz_compress_batch_host(cz_context* c, const void* in_base, size_t in_bytes, const uint64_t* in_off, const uint64_t* in_len, size_t n,
+                                     void* out_base, size_t out_bytes, const uint64_t* out_off, const uint64_t* out_cap, uint32_t flags,
+                                     cz_compress_result* results) {
+    if (!c || (flags & ~CZ_COMPRESS_CHECKSUM)) return CZ_E_INVALID_ARG;
+    if (n == 0) return CZ_OK;
+    return cz_compress_staged(c, in_base, in_bytes, in_off, in_len, n, out_base, out_bytes, out_off, out_cap, nullptr, results,
+        [&](const void* i, const uint64_t* io, const uint64_t* il, void* o, const uint64_t* oo, const uint64_t* oc, const uint32_t*, cz_compress_result* r) {
+            return cz_compress_batch_device(c, i, io, il, n, o, oo, oc, flags, r);
+        });
+}
+
+/* ------------------------------------------------------------------ compression with dictionaries */
+/* Prepares `d` for compression once: the image is zeroed, then cz_enc_dict_prep_kernel fills it. */
+static int cz_enc_dict_prepare(cz_context* c, cz_dictionary* d) {
+    if (d->d_enc) return CZ_OK;
+    CzeDict* img = nullptr;
+    CZ_HIP(c, hipMalloc((void**)&img, sizeof(CzeDict)));
+    const uint64_t D = d->len - d->content_off, span = D < CZE_WINDOW ? D : CZE_WINDOW;
+    const unsigned grid = (unsigned)(span / (16 * CZE_THREADS) + 1);   /* ~16 positions per thread */
+    if (hipMemsetAsync(img, 0, sizeof(CzeDict), c->stream) != hipSuccess) { c->last_hip_error = (int)hipGetLastError(); (void)hipFree(img); return CZ_E_HIP; }
+    hipLaunchKernelGGL(cz_enc_dict_prep_kernel, dim3(grid), dim3(CZE_THREADS), 0, c->stream, (const cz_device_frame_state*)d->d_state,
+                       (const uint8_t*)(d->d_raw + d->content_off), D, img);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { c->last_hip_error = (int)hipGetLastError(); (void)hipFree(img); return CZ_E_HIP; }
+    d->d_enc = img;
+    return CZ_OK;
+}
+
+CZ_EXPORT int cz_context_set_compress_dictionaries(cz_context* c, const cz_dictionary* const* dicts, size_t k) try {
+    if (!c || (k && !dicts) || k > CZ_MAX_DICTIONARIES) return CZ_E_INVALID_ARG;
+    for (size_t i = 0; i < k; i++) if (!dicts[i] || dicts[i]->ctx != c) return CZ_E_INVALID_ARG;
+    CZ_HIP(c, hipSetDevice(c->device));
+    CZ_HIP(c, hipStreamSynchronize(c->stream));                         /* launches in flight may still read the old table */
+    std::vector<cze_dict_entry> t(k);
+    for (size_t i = 0; i < k; i++) {
+        cz_dictionary* d = const_cast<cz_dictionary*>(dicts[i]);        /* (the prepared image is a cache kept with the dictionary) */
+        const int st = cz_enc_dict_prepare(c, d); if (st) return st;
+        t[i].img = d->d_enc; t[i].content = d->d_raw + d->content_off; t[i].content_len = d->len - d->content_off; t[i].id = d->id;
+        for (int j = 0; j < 3; j++) t[i].rep[j] = d->hist[j];
+    }
+    cze_dict_entry* table = nullptr;
+    if (k) {
+        CZ_HIP(c, hipMalloc((void**)&table, k * sizeof(cze_dict_entry)));
+        if (hipMemcpy(table, t.data(), k * sizeof(cze_dict_entry), hipMemcpyHostToDevice) != hipSuccess) { c->last_hip_error = (int)hipGetLastError(); (void)hipFree(table); return CZ_E_HIP; }
+    }
+    if (c->enc_dicts) (void)hipFree(c->enc_dicts);
+    c->enc_dicts = table; c->enc_dict_count = (uint32_t)k;
+    return CZ_OK;
+} catch (const std::bad_alloc&) { return CZ_E_OUT_OF_MEMORY; }
+
+CZ_EXPORT int cz_compress_batch_dict_device(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
+                                            void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
+                                            const uint32_t* d_dict_index, cz_compress_result* d_results) {
+    if (!c || (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_NO_DICT_ID)) || n > 0xFFFFFFFFull) return CZ_E_INVALID_ARG;
+    if (!d_dict_index && c->enc_dict_count != 1) return CZ_E_INVALID_ARG;
+    if (n == 0) return CZ_OK;
+    if (!d_in_base || !d_in_off || !d_in_len || !d_out_base || !d_out_off || !d_out_cap || !d_results) return CZ_E_INVALID_ARG;
+    CZ_HIP(c, hipSetDevice(c->device));
+    if (!c->enc_dgrid) {
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_frames_dict_kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
+        c->enc_dgrid = c->num_cu * occ;
+    }
+    const int grid = (size_t)c->enc_dgrid < n ? c->enc_dgrid : (int)n;
+    const int st = cz_enc_reserve(c, grid); if (st) return st;
+    cz_enc_args a; memset(&a, 0, sizeof a);
+    a.in_base = (const uint8_t*)d_in_base; a.in_off = d_in_off; a.in_len = d_in_len;
+    a.out_base = (uint8_t*)d_out_base; a.out_off = d_out_off; a.out_cap = d_out_cap; a.results = d_results;
+    a.n = (uint32_t)n; a.flags = flags; a.work_counter = c->enc_counter; a.scratch = c->enc_scratch; a.scratch_stride = CZE_SCRATCH_BYTES;
+    cz_enc_dargs dd; memset(&dd, 0, sizeof dd);
+    dd.dicts = c->enc_dicts; dd.dict_index = d_dict_index; dd.ndicts = c->enc_dict_count;
+    hipLaunchKernelGGL(cz_compress_frames_dict_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, a, dd);
+    CZ_HIP(c, hipGetLastError());
+    c->last_grid = grid;
+    return CZ_OK;
+}
+
+CZ_EXPORT int cz_compress_batch_dict_host(cz_context* c, const void* in_base, size_t in_bytes, const uint64_t* in_off, const uint64_t* in_len, size_t n,
+                                          void* out_base, size_t out_bytes, const uint64_t* out_off, const uint64_t* out_cap, uint32_t flags,
+                                          const uint32_t* dict_index, cz_compress_result* results) {
+    if (!c || (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_NO_DICT_ID))) return CZ_E_INVALID_ARG;
+    if (!dict_index && c->enc_dict_count != 1) return CZ_E_INVALID_ARG;
+    if (n == 0) return CZ_OK;
+    return cz_compress_staged(c, in_base, in_bytes, in_off, in_len, n, out_base, out_bytes, out_off, out_cap, dict_index, results,
+        [&](const void* i, const uint64_t* io, const uint64_t* il, void* o, const uint64_t* oo, const uint64_t* oc, const uint32_t* di, cz_compress_result* r) {
+            return cz_compress_batch_dict_device(c, i, io, il, n, o, oo, oc, flags, di, r);
+        });
 }
 
 /* ------------------------------------------------------------------ several devices */
@@ -1349,6 +1449,7 @@ CZ_EXPORT void cz_dictionary_destroy(cz_dictionary* d) {
     (void)hipStreamSynchronize(d->ctx->stream);
     if (d->d_raw) (void)hipFree(d->d_raw);
     if (d->d_state) (void)hipFree(d->d_state);
+    if (d->d_enc) (void)hipFree(d->d_enc);
     delete d;
 }
 /* Batch decodes of this context start every frame from `d` (NULL: from nothing, the default). */

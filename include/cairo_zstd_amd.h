@@ -457,6 +457,35 @@ int cz_compress_batch_host(cz_context* ctx, const void* in_base, size_t in_bytes
                            void* out_base, size_t out_bytes, const uint64_t* out_off, const uint64_t* out_cap, uint32_t flags,
                            cz_compress_result* results);
 
+/*
+ * Compression with dictionaries, the write side of cz_context_set_dictionaries: set the dictionaries once, then
+ * run many batches.  A frame written with dictionary j names it by a Dictionary_ID field (1, 2 or 4 bytes, the smallest that holds
+ * cz_dictionary_id; none for ID 0 or with CZ_COMPRESS_NO_DICT_ID), its matches may reach into the dictionary's content, its repeat
+ * offsets start from the dictionary's three, and its first Compressed blocks may use the dictionary's Huffman code (Treeless
+ * literals) and its LL / OF / ML tables (Repeat mode) while the frame has not replaced them.  Decode such frames with
+ * cz_context_set_dictionaries (or cz_context_set_dictionary / init_from_dict).  cz_compress_bound still holds.
+ */
+#define CZ_COMPRESS_NO_DICT     0xFFFFFFFFu  /* dict_index entry: this frame is written without a dictionary */
+#define CZ_COMPRESS_NO_DICT_ID  2u           /* flag: omit the Dictionary_ID field (like ZSTD_c_dictIDFlag = 0) */
+/* The dictionaries later cz_compress_batch_dict_* calls on this context pick from (k == 0: none).  Prepares each dictionary for
+ * compression the first time it is set (a hash table of its content and encode forms of its tables, kept with the dictionary and
+ * freed by cz_dictionary_destroy).  CZ_E_INVALID_ARG when dicts is NULL with k > 0, an entry is NULL, a dictionary belongs to
+ * another context, or k > CZ_MAX_DICTIONARIES; on any error the previous setting stays in force.  Independent of the decode
+ * settings (cz_context_set_dictionary / _dictionaries).  Synchronises the context's stream; the dictionaries must outlive the launches. */
+int cz_context_set_compress_dictionaries(cz_context* ctx, const cz_dictionary* const* dicts, size_t k);
+/* As cz_compress_batch_device; frame i uses dicts[dict_index[i]] of the last cz_context_set_compress_dictionaries, or none for
+ * CZ_COMPRESS_NO_DICT (the frame then comes out byte for byte as from cz_compress_batch_device).  Any other index >= k fails that
+ * frame alone with CZ_E_INVALID_ARG (nothing written), as does a dictionary content plus input of 4 GiB - 1 MiB or more.
+ * d_dict_index (DEVICE, n entries) may be NULL when exactly one dictionary is set: every frame uses it.  flags: CZ_COMPRESS_CHECKSUM,
+ * CZ_COMPRESS_NO_DICT_ID. */
+int cz_compress_batch_dict_device(cz_context* ctx, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
+                                  void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
+                                  const uint32_t* d_dict_index, cz_compress_result* d_results);
+/* Same with HOST buffers (dict_index too), as cz_compress_batch_host. */
+int cz_compress_batch_dict_host(cz_context* ctx, const void* in_base, size_t in_bytes, const uint64_t* in_off, const uint64_t* in_len, size_t n,
+                                void* out_base, size_t out_bytes, const uint64_t* out_off, const uint64_t* out_cap, uint32_t flags,
+                                const uint32_t* dict_index, cz_compress_result* results);
+
 #ifdef __cplusplus
 }
 #endif
