@@ -20,7 +20,7 @@ from . import status
 from ._lib import (COMPRESS_CHECKSUM, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
                    BlockHeader, FrameHeader, build, lib)
 
-DEBUG_CHAIN_CPP_STEP, DEBUG_NO_HUF1, DEBUG_WX_POISON, DEBUG_EXEC_FIRST = 1, 2, 4, 8     # cz_context_set_debug_flags
+DEBUG_CHAIN_CPP_STEP, DEBUG_NO_HUF1, DEBUG_WX_POISON, DEBUG_EXEC_FIRST, DEBUG_EXEC_LEAVE = 1, 2, 4, 8, 16     # cz_context_set_debug_flags
 from .status import CzError
 
 __all__ = ["Context", "FrameDecoder", "BlockDecodingStrategy", "decode_batch_host", "read_frame_header",
@@ -167,7 +167,7 @@ class Context:
         return int(a.value), int(b.value)
 
     def set_debug_flags(self, flags: int):
-        """Test knobs (cz_context_set_debug_flags): DEBUG_CHAIN_CPP_STEP, DEBUG_NO_HUF1, DEBUG_WX_POISON."""
+        """Test knobs (cz_context_set_debug_flags): DEBUG_CHAIN_CPP_STEP, DEBUG_NO_HUF1, DEBUG_WX_POISON, DEBUG_EXEC_FIRST, DEBUG_EXEC_LEAVE."""
         lib().cz_context_set_debug_flags(self._h, int(flags))
 
     def debug_read_chain_arena(self, nbytes: int):
@@ -215,6 +215,15 @@ class Context:
         """(frames listed for cz_wexec_kernel, frames it finished, frames it handed on) in the last launch."""
         a, b, c = C.c_size_t(), C.c_size_t(), C.c_size_t()
         lib().cz_context_last_wexec_counts(self._h, C.byref(a), C.byref(b), C.byref(c))
+        return int(a.value), int(b.value), int(c.value)
+
+    def last_side_counts(self):
+        """(workgroups of cz_wexec_kernel that counted themselves in, waves of cz_execute_frames_kernel that left the CUs to it, waves
+        that waited for it and stayed) in the last launch, side by side."""
+        a, b, c = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        st = lib().cz_context_last_side_counts(self._h, C.byref(a), C.byref(b), C.byref(c))
+        if st:
+            raise CzError(st, "cz_context_last_side_counts")
         return int(a.value), int(b.value), int(c.value)
 
     def last_wexec_ms(self) -> float:

@@ -128,6 +128,8 @@ def lib() -> C.CDLL:
     L.cz_context_last_fallback_count.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.cz_context_last_wexec_counts.restype = C.c_int
     L.cz_context_last_wexec_counts.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.cz_context_last_side_counts.restype = C.c_int
+    L.cz_context_last_side_counts.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.cz_context_last_wexec_ms.restype = C.c_int
     L.cz_context_last_wexec_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.cz_context_last_prepass_counts.restype = C.c_int

@@ -460,10 +460,26 @@ CZ_EXPORT int cz_context_last_wexec_counts(cz_context* c, size_t* listed, size_t
     CZ_HIP(c, hipStreamSynchronize(c->stream));
     uint32_t h[4] = {0, 0, 0, 0};
     CZ_HIP(c, hipMemcpy(h, c->scan_ctl + 206, sizeof h, hipMemcpyDeviceToHost));
-    if (getenv("CZ_SIDE_COUNTS")) { uint32_t g[4] = {0, 0, 0, 0}; (void)hipMemcpy(g, c->scan_ctl + 213, sizeof g, hipMemcpyDeviceToHost); fprintf(stderr, "side counts: wexec workgroups counted in %u, (early %u), execute waves that left %u, that waited and stayed %u\n", g[0], g[1], g[2], g[3]); }
     if (listed) *listed = h[0];
     if (given_up) *given_up = h[1];
     if (finished) *finished = h[3];
+    return CZ_OK;
+}
+/* Diagnostics of the most recent batch launch (synchronises), side by side: workgroups of cz_wexec_kernel's later launch that counted
+   themselves in, waves of cz_execute_frames_kernel that left the CUs to it, waves that waited for it and stayed. */
+CZ_EXPORT int cz_context_last_side_counts(cz_context* c, size_t* wexec_in, size_t* exec_left, size_t* exec_waited) {
+    if (!c) return CZ_E_INVALID_ARG;
+    if (wexec_in) *wexec_in = 0;
+    if (exec_left) *exec_left = 0;
+    if (exec_waited) *exec_waited = 0;
+    if (!c->scan_ctl) return CZ_OK;
+    CZ_HIP(c, hipSetDevice(c->device));
+    CZ_HIP(c, hipStreamSynchronize(c->stream));
+    uint32_t h[4] = {0, 0, 0, 0};
+    CZ_HIP(c, hipMemcpy(h, c->scan_ctl + 213, sizeof h, hipMemcpyDeviceToHost));
+    if (wexec_in) *wexec_in = h[0];
+    if (exec_left) *exec_left = h[2];
+    if (exec_waited) *exec_waited = h[3];
     return CZ_OK;
 }
 /* Diagnostics of the most recent batch launch (synchronises): entries on the fall-back list, i.e. frames the pre-pass and execute
@@ -736,8 +752,7 @@ static int cz_enqueue(cz_context* c, const cz_batch_args& proto, size_t n, hipSt
                 hipLaunchKernelGGL(czx8::cz_execute_frames8_kernel, dim3(egrid8), dim3(CZ_WG_THREADS), CZ_EXEC_DYN_LDS, sx, a);   /* (only one of the two builds does anything) */
                 CZ_HIP(c, hipGetLastError());
                 CZ_HIP(c, hipEventRecord(split ? c->ev_x4 : c->ev_join, sx));
-                if (exec_first) {
-                    CZ_HIP(c, hipEventRecord(c->ev_fork, sx));          /* (free by now: an event behind the other kernel's SUBMISSION is the best a host can do to put this one second) */
+                if (exec_first) {                                       /* (only the host's submission order: where the dispatcher places each kernel is its own affair) */
                     CZ_HIP(c, hipStreamWaitEvent(s0, cap ? c->ev_lit_dep : c->ev_lit, 0));
                     hipLaunchKernelGGL(cz_wexec_kernel, dim3(wgrid), dim3(WX_THREADS), WX_LDS_BYTES, s0, a);
                     CZ_HIP(c, hipGetLastError());

@@ -89,9 +89,10 @@ __device__ static inline int cz_wx_big_only(const cz_batch_args& a) {
    the first wave of the other kernel asks, nobody leaves, and the placement is the dispatcher's, which measured 0.1 ms faster on
    config 4a than any split by id (profiles/r5/NOTES.md); dispatched second, it finds the even CUs free.  On this part every XCD has
    4 shader engines x 8 active CUs with ids 0..8, 128 even and 128 odd (scripts/micro/census.hip).  1: even, 0: odd; the CPU emulator
-   runs the kernels one after the other and has no CUs: 2. */
+   runs the kernels one after the other and has no CUs: 2.  The s_getreg encodings and the even / odd split are gfx950 facts: any
+   other target gets 2 as well (no side). */
 __device__ static inline uint32_t cz_cu_side() {
-#if defined(CZ_EMU) || !defined(__HIP_DEVICE_COMPILE__)
+#if defined(CZ_EMU) || !defined(__HIP_DEVICE_COMPILE__) || !defined(__gfx950__)
     return 2u;
 #else
 #ifndef CZ_CU_SIDE_RULE
@@ -2572,15 +2573,35 @@ extern "C" __global__ void __launch_bounds__(CZ_WG_THREADS, CZ_EXEC_WAVES) CZ_EX
     const int wx_on = !early && ::cz_wx_side_by_side(a), wx_big = !early && ::cz_wx_big_only(a);
     /* side by side: cz_wexec_kernel needs whole CUs.  A wave that finds itself on an even CU gives that kernel's workgroups a few
        microseconds to count themselves in (scan_ctl[213] of args.wx_cus: dispatched first, as usual, they are there and nobody
-       leaves); if they are not, this kernel was placed first and holds every CU: the waves on the even ones leave (cz_cu_side) */
+       leaves); if they are not, this kernel was placed first and holds every CU: the waves on the even ones leave (cz_cu_side).
+       Only when cz_scan_kernel listed frames (scan_ctl[206]): with none, cz_wexec_kernel returns before it counts itself in, and a
+       wave that waited for it would always leave.  Leaving can never lose a frame: the frames come from one shared counter
+       (exec_counter), and a wave leaves only if the count of leavers (scan_ctl[215]) stays below gridDim.x with it — the wave whose
+       leave would make it reach gridDim.x stays instead.  So at least one wave of the launch stays, and it pulls frames until the
+       counter is past the batch: every frame is met by a wave that stays, whatever the placement or the reason wx_cus is not
+       reached (another context on the device, more wexec CUs than even CUs, CU masks, the other submission order).
+       CZ_DEBUG_EXEC_LEAVE (test knob): every wave takes the leave branch at once, as if it were on an even CU nobody met. */
+    if (wx_on) {
+        uint32_t leave = (a.debug_flags & CZ_DEBUG_EXEC_LEAVE) != 0u;
 #if !defined(CZ_EXP_NO_SIDE) && !defined(CZ_EMU)                       /* (the emulator runs the kernels one after the other: no CUs to share) */
-    if (wx_on && ::cz_cu_side() == 1u) {
-        uint32_t polls = 0;
-        while (*(volatile uint32_t*)&a.scan_ctl[213] < a.wx_cus && polls < 8u) { __builtin_amdgcn_s_sleep(127); polls++; }
-        if (*(volatile uint32_t*)&a.scan_ctl[213] < a.wx_cus) { if (LANE == 0) atomicAdd(&a.scan_ctl[215], 1u); return; }
-        if (polls && LANE == 0) atomicAdd(&a.scan_ctl[216], 1u);
-    }
+        if (!leave && cz_uni(a.scan_ctl[206]) != 0u && ::cz_cu_side() == 1u) {
+            uint32_t polls = 0;
+            while (*(volatile uint32_t*)&a.scan_ctl[213] < a.wx_cus && polls < 8u) { __builtin_amdgcn_s_sleep(127); polls++; }
+            leave = cz_uni((uint32_t)(*(volatile uint32_t*)&a.scan_ctl[213] < a.wx_cus));
+            if (!leave && polls && LANE == 0) atomicAdd(&a.scan_ctl[216], 1u);
+        }
 #endif
+        if (leave) {
+            __syncthreads();
+            if (LANE == 0) {
+                const uint32_t left = atomicAdd(&a.scan_ctl[215], 1u) + 1u;
+                if (left >= gridDim.x) atomicAdd(&a.scan_ctl[215], 0xFFFFFFFFu);   /* the last one: stays (and is not counted) */
+                sh.frame_idx = left < gridDim.x;
+            }
+            __syncthreads();
+            if (cz_uni(sh.frame_idx)) return;
+        }
+    }
     cz_init_llml();
     for (;;) {
         __syncthreads();

@@ -75,7 +75,9 @@ typedef struct cz_blk_desc {
                                   [208] listed frames claimed so far (by either execute kernel), [209] frames cz_wexec_kernel finished,
                                   [210] listed frames of CZ_WX_BIG_UNITS and more (the first CZ_WX_BIG_MAX of them carry CZ_PRE_WXBIG),
                                   [211] frames marked CZ_PRE_EARLY, [212] work counter of the small-block launch of cz_chain_kernel (args.chain_part 2),
-                                  [213] workgroups of cz_wexec_kernel that stayed (at most args.wx_cus), [214] the same for its early launch */
+                                  [213] workgroups of cz_wexec_kernel that stayed (at most args.wx_cus), [214] the same for its early launch,
+                                  [215] waves of cz_execute_frames_kernel that left to cz_wexec_kernel (side by side; never all of a launch),
+                                  [216] waves of it that waited for cz_wexec_kernel and stayed */
 /* The chain pre-pass runs as TWO launches of cz_chain_kernel (args.chain_part): part 1 the LARGE blocks — CZ_BIG_BLOCK_SEQS sequences and
    more: the head of the block list, which is sorted by size class — part 2 all others.  A batch is as long as its longest chain
    (sequences x ~95 ns), and on ragged batches that is ONE block: with the small blocks in a launch of their own, everything that

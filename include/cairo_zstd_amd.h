@@ -210,6 +210,9 @@ int cz_context_last_sequence_stats(cz_context* ctx, uint64_t* near_offsets, uint
 /* Diagnostics of the most recent batch launch (synchronises): frames listed for cz_wexec_kernel, frames it finished, frames it
  * handed on to cz_decode_frames_kernel. */
 int cz_context_last_wexec_counts(cz_context* ctx, size_t* listed, size_t* finished, size_t* given_up);
+/* Diagnostics of the most recent batch launch (synchronises), side by side: workgroups of cz_wexec_kernel that counted themselves in,
+ * waves of cz_execute_frames_kernel that left the CUs to it (never every wave of a launch), waves that waited for it and stayed. */
+int cz_context_last_side_counts(cz_context* ctx, size_t* wexec_in, size_t* exec_left, size_t* exec_waited);
 /* The chain pre-pass of a batch is two launches of cz_chain_kernel — the LARGE blocks (4 096 sequences and more: a batch lasts as
  * long as its longest chain, sequence_section_decoder.cairo:223-286) on one stream, all others on another — and the execute stage
  * starts behind the second: cz_execute_frames_kernel on every frame without a large block, cz_wexec_kernel on the batch's large
@@ -252,6 +255,8 @@ int cz_context_last_wexec_ms(cz_context* ctx, float* ms);
                                        bound of its polling loop (WX_SPIN_LIMIT) and the frame is handed to cz_decode_frames_kernel: the test of that bound */
 #define CZ_DEBUG_EXEC_FIRST 8u      /* side by side: cz_execute_frames_kernel is submitted AHEAD of cz_wexec_kernel (normally behind it): the two keep to their halves
                                        of the CUs by the hardware's CU id, so the frames split the same way in either order — the test of that */
+#define CZ_DEBUG_EXEC_LEAVE 16u     /* side by side: every wave of cz_execute_frames_kernel takes the leave branch at once, as if it were on an even CU that
+                                       cz_wexec_kernel never met — the worst placement, made deterministic: the last wave stays and every frame is still decoded */
 int cz_context_set_debug_flags(cz_context* ctx, uint32_t flags);
 /* Copies the first `bytes` of the chain arena (headers, state -> code maps and per-sequence records of the most recent batch
  * launch, as cz_chain_kernel left them) to host memory and returns the arena units in use; synchronises.  For tests. */

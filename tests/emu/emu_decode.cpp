@@ -84,7 +84,7 @@ int main(int argc, char** argv) {
     /* exact-size heap blocks so that ASan sees any byte read or written out of range */
     uint8_t* in_exact = (uint8_t*)malloc(in.size() ? in.size() : 1); if (in.size()) memcpy(in_exact, in.data(), in.size());
     uint8_t* out = (uint8_t*)malloc(out_total ? out_total : 1); memset(out, 0xEE, out_total);
-    std::vector<cz_frame_result> res(n);
+    std::vector<cz_frame_result> res(n); if (n) memset(res.data(), 0xFF, n * sizeof(cz_frame_result));   /* poisoned: a frame no kernel decoded shows */
     uint32_t counter = 0;
     const int grid = 2;
     uint8_t* lit = (uint8_t*)malloc((size_t)grid * CZ_WG_SCRATCH_BYTES);
@@ -218,7 +218,7 @@ int main(int argc, char** argv) {
         for (uint32_t i = 0; i < fallback_count && i < n; i++) { if (fallback_list[i] >= n || seen[fallback_list[i]]++) { fprintf(stderr, "EMU_EXEC: frame %u is on the fall-back list twice (or not a frame)\n", fallback_list[i]); return 4; } }
         if (fallback_count > n) { fprintf(stderr, "EMU_EXEC: %u entries on the fall-back list of %llu frames\n", fallback_count, (unsigned long long)n); return 4; }
     }
-    if (wx_waves > 0) { unsigned long long nd = 0; for (uint64_t i = 0; i < n; i++) nd += (frame_pre[i] & CZ_PRE_WXDONE) != 0; fprintf(stderr, "EMU_WEXEC: %u frames listed, %llu finished by cz_wexec_kernel\n", scan_ctl[206], nd); }
+    if (wx_waves > 0) { unsigned long long nd = 0; for (uint64_t i = 0; i < n; i++) nd += (frame_pre[i] & CZ_PRE_WXDONE) != 0; fprintf(stderr, "EMU_WEXEC: %u frames listed, %llu finished by cz_wexec_kernel, %u execute waves left\n", scan_ctl[206], nd, scan_ctl[215]); }
     FILE* g = fopen(argv[2], "wb"); if (!g) return 2;
     for (uint64_t i = 0; i < n; i++) {
         fwrite(&res[i], sizeof(cz_frame_result), 1, g);

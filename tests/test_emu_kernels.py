@@ -322,3 +322,76 @@ def test_emu_prepass_kernels_and_divergence_vectors():
         _run_and_compare(frames[:6], caps[:6], chain_bytes=8 << 20, lit_bytes=4 << 20, exec_kernel=True)
     finally:
         del os.environ["EMU_SEGS"]
+
+
+def _waves_left(err):
+    return int(err.split("finished by cz_wexec_kernel, ")[1].split()[0])
+
+
+def test_emu_execute_waves_that_leave_never_lose_a_frame():
+    """Side by side, a wave of cz_execute_frames_kernel on an even CU that cz_wexec_kernel's workgroups never meet leaves (scan_ctl[215]).
+    CZ_DEBUG_EXEC_LEAVE makes every wave take that branch, and the emulator runs the two workgroups of the launch one after the other:
+    the first leaves, the second would make the count reach the grid and stays, and it alone executes every frame cz_wexec_kernel
+    does not take.  Corpus, synthetic and damaged frames, with cz_wexec_kernel forced on, in both orders; the results start poisoned,
+    so a frame nobody decoded fails the comparison."""
+    import cairo_zstd_amd as cz
+    frames, caps = [], []
+    for name, z, orig in corpus_pairs(max_orig=2500):
+        frames.append(z)
+        caps.append(len(orig) + 16)
+    b = synth.generate("mix", 30, first_index=0, nthreads=2)
+    keep = [i for i in range(b.n) if b.regen[i] < 30000][:6]
+    frames += [b.frame(i) for i in keep]
+    caps += [int(b.regen[i]) + 8 for i in keep]
+    for idx, (name, z, orig) in enumerate(corpus_pairs(max_orig=700)):
+        rng = np.random.default_rng(1700 + idx)
+        a = bytearray(z)
+        a[int(rng.integers(0, len(a)))] ^= 1 << int(rng.integers(0, 8))
+        frames.append(bytes(a))
+        caps.append(len(orig) * 2 + 4096)
+        frames.append(z[: len(z) // 2])
+        caps.append(len(orig) * 2 + 4096)
+    for exec_first in ("0", "1"):
+        os.environ["EMU_EXEC_FIRST"] = exec_first
+        try:
+            _run_and_compare(frames, caps, chain_bytes=16 << 20, lit_bytes=8 << 20, exec_kernel=True, wexec_waves=4, verify=False,
+                             debug_flags=cz.DEBUG_EXEC_LEAVE)
+        finally:
+            del os.environ["EMU_EXEC_FIRST"]
+        err = emu_runner.run.last_stderr
+        assert int(err.split("EMU_WEXEC: ")[1].split()[0]) > 10, err   # frames were listed for cz_wexec_kernel ...
+        assert _waves_left(err) == 1, err                                # ... and one of the two execute waves left
+
+
+def test_emu_execute_waves_leave_when_nothing_is_listed():
+    """Every frame checksummed and the checksum verified on the device: cz_scan_kernel lists nothing, so cz_wexec_kernel returns
+    at once, and every wave of cz_execute_frames_kernel takes the leave branch (CZ_DEBUG_EXEC_LEAVE).  The last wave stays and
+    executes the whole batch: every frame matches the oracle, XXH64 included."""
+    import cairo_zstd_amd as cz
+    from conftest import add_checksum
+    frames, caps = [], []
+    for name, z, orig in corpus_pairs(max_orig=2500)[:12]:               # (the corpus frames carry a checksum)
+        frames.append(z)
+        caps.append(len(orig) + 16)
+    b = synth.generate("mix", 30, first_index=0, nthreads=2)
+    for i in [i for i in range(b.n) if b.regen[i] < 30000][:4]:
+        z = b.frame(i)
+        if not z[4] & 4:
+            z = add_checksum(z, oracle.decode_frame(z, cap=int(b.regen[i]))[1])
+        frames.append(z)
+        caps.append(int(b.regen[i]) + 8)
+    rng = np.random.default_rng(11)
+    frames.append(raw_frame_with_checksum(rng.integers(0, 256, 3000, dtype=np.uint8).tobytes()))
+    caps.append(3008)
+    assert all(z[4] & 4 for z in frames)
+    for exec_first in ("0", "1"):
+        os.environ["EMU_EXEC_FIRST"] = exec_first
+        try:
+            _run_and_compare(frames, caps, chain_bytes=16 << 20, lit_bytes=8 << 20, exec_kernel=True, wexec_waves=4, verify=True,
+                             debug_flags=cz.DEBUG_EXEC_LEAVE)
+        finally:
+            del os.environ["EMU_EXEC_FIRST"]
+        err = emu_runner.run.last_stderr
+        assert int(err.split("EMU_WEXEC: ")[1].split()[0]) == 0, err   # nothing listed
+        assert _waves_left(err) == 1, err
+        assert int(err.split("EMU_EXEC: ")[1].split()[0]) == len(frames), err   # all executed by the wave that stayed, none handed on

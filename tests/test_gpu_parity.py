@@ -725,7 +725,8 @@ def test_side_by_side_split_does_not_depend_on_submission_order(cz):
     """Side by side, cz_wexec_kernel and cz_execute_frames_kernel each keep to one half of the CUs by the hardware's CU id (cz_cu_side):
     whichever kernel the host submits first, cz_wexec_kernel gets its CUs and finishes a comparable share of a far-offset batch
     (round 4: submitted second it found every CU held by the other kernel's persistent waves and finished next to nothing).  Outputs
-    against the oracle in both orders."""
+    against the oracle in both orders.  DEBUG_EXEC_FIRST exercises only the HOST's submission order: no event orders the two
+    kernels, and where the dispatcher places each of them is not under the host's control."""
     from cairo_zstd_amd import synth
     b = synth.generate("full_4a", 3000, first_index=5)
     frames, caps = [b.frame(i) for i in range(b.n)], [int(r) for r in b.regen]
