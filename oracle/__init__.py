@@ -94,6 +94,8 @@ def lib() -> C.CDLL:
         L.czo_kat_huf_table.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32)]
         L.czo_set_d1_reference_nibbles.argtypes = [C.c_int]
+        L.czo_dump_sequences.restype = C.c_int
+        L.czo_dump_sequences.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.czo_libzstd_batch.restype = C.c_long
         L.czo_libzstd_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         _lib = L
@@ -122,6 +124,34 @@ def decode_frame(src, cap: int | None = None):
     d = dict(written=info[0], consumed=info[1], checksum=info[2], has_checksum=bool(info[3]), blocks=info[4],
              window_size=info[5], content_size=info[6])
     return st, out[: info[0]].tobytes(), d
+
+
+def huf_code_lengths(desc):
+    """The Huffman tree description at the start of `desc` read by the oracle (huff0 table build).  Returns (status, code length
+    per symbol 0..255 (0: no code), bytes the description used)."""
+    a = _buf(desc)
+    sym = np.zeros(1 << 12, dtype=np.uint8)
+    nb = np.zeros(1 << 12, dtype=np.uint8)
+    w = np.zeros(256, dtype=np.uint8)
+    mb, used, nw = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    st = lib().czo_kat_huf_table(a.ctypes.data, a.size, sym.ctypes.data, nb.ctypes.data, C.byref(mb), C.byref(used), w.ctypes.data,
+                                 C.byref(nw))
+    lengths = [0] * 256
+    if st == 0:
+        for i in range(1 << mb.value):
+            lengths[int(sym[i])] = int(nb[i])
+    return st, lengths, used.value
+
+
+def dump_sequences(src, cap: int, max_sequences: int = 1 << 20):
+    """Every sequence of a frame as the oracle decodes it, in order across blocks: (status, [(literal length, match length,
+    Offset_Value)])."""
+    a = _buf(src)
+    out = np.zeros(3 * max_sequences, dtype=np.uint32)
+    n = C.c_size_t()
+    st = lib().czo_dump_sequences(a.ctypes.data, a.size, cap, out.ctypes.data, max_sequences, C.byref(n))
+    k = min(n.value, max_sequences)
+    return st, [tuple(int(v) for v in out[3 * i:3 * i + 3]) for i in range(k)]
 
 
 def decode_single_block(src, cap: int = 1 << 20, window: int = 1 << 17):
