@@ -24,6 +24,7 @@ COMPRESS_RESULT_DTYPE = np.dtype([("status", "<i4"), ("blocks", "<u4"), ("bytes_
 assert COMPRESS_RESULT_DTYPE.itemsize == 32
 COMPRESS_CHECKSUM = 1
 COMPRESS_NO_DICT_ID = 2                 # omit the Dictionary_ID field (cz_compress_batch_dict_*)
+COMPRESS_SPLIT = 4                      # cut inputs longer than compress_split_segment() into segments compressed side by side
 COMPRESS_NO_DICT = 0xFFFFFFFF           # dict_index entry: no dictionary for this buffer
 
 
@@ -45,7 +46,7 @@ class BlockHeader(C.Structure):
 
 def build(force: bool = False) -> str:
     """Compile the library in-tree with hipcc for gfx950 (csrc/Makefile)."""
-    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_enc.hip", "czstd_types.h", "czstd_dict.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_enc.hip", "czstd_encsplit.hip", "czstd_types.h", "czstd_dict.h")]
     srcs += [os.path.join(_HERE, "..", "include", f) for f in ("cairo_zstd_amd.h", "cairo_zstd_amd_status.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -148,6 +149,9 @@ def lib() -> C.CDLL:
     L.cz_decode_batch_host.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp]
     L.cz_compress_bound.restype = C.c_uint64
     L.cz_compress_bound.argtypes = [C.c_uint64]
+    if hasattr(L, "cz_compress_split_segment"):                         # (diagnostic builds of earlier sources lack it)
+        L.cz_compress_split_segment.restype = C.c_uint64
+        L.cz_compress_split_segment.argtypes = []
     L.cz_compress_batch_device.restype = C.c_int
     L.cz_compress_batch_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, C.c_uint32, vp]
     L.cz_compress_batch_host.restype = C.c_int

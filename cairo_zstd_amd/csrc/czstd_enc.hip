@@ -21,6 +21,11 @@
  * cz_enc_dict_prep_kernel prepared once: Dictionary_ID in the header, matches into the content, the dictionary's repeat offsets,
  * Treeless literals and Repeat-mode sequence tables while the frame has not replaced them.
  *
+ * CZ_COMPRESS_SPLIT (czstd_encsplit.hip, included behind this file) cuts a large input into segments that different
+ * workgroups compress side by side into one frame.  Its kernel runs the same per-block pipeline from a function of its own; the two
+ * kernels here keep their bodies.  cze_literals and cze_sequences carry a second template parameter only so that it gets copies of
+ * its own and these kernels compile to the same code as without it.
+ *
  * Written so that the CPU SIMT emulator of tests/emu (hip/hip_runtime.h) builds it unchanged.  Needs czstd_kernels.hip first
  * (XXH64 rounds, the LL / ML code tables and the Predefined distributions).
  */
@@ -358,8 +363,9 @@ __device__ static inline uint32_t cze_dfse_step(CzeBits& w, const CzeDict* img, 
 }
 /* the sequences section of n sequences at out[0, lim); returns its length, or lim + 1 when it does not fit.  Predefined modes;
    with a dictionary (DICT), Repeat for each field of `live` (bit 0 LL, 1 OF, 2 ML: the dictionary's table is still the decoder's)
-   whose dictionary table has a state for every code of the block.  *rep_out: the fields written as Repeat. */
-template <bool DICT>
+   whose dictionary table has a state for every code of the block.  *rep_out: the fields written as Repeat.  USER: a copy of its own
+   for another kernel (czstd_encsplit.hip), so that this file's kernels compile as they did without it. */
+template <bool DICT, int USER = 0>
 __device__ static uint32_t cze_sequences(const CzeSeq* sq, uint32_t n, uint32_t nlit, uint8_t* out, uint32_t lim, const CzeDict* img,
                                          uint32_t live, uint32_t* rep_out) {
     uint32_t h = 0, rm = 0;
@@ -436,8 +442,9 @@ __device__ static uint64_t cze_xxh64(const uint8_t* p, uint64_t len) {
 /* ------------------------------------------------------------------ one block */
 /* literals section of lit[0, nlit) at out (room: lim); returns its length; Raw, RLE or Huffman (1 stream below 1 KiB, else 4).
    With a dictionary (DICT) whose Huffman code is still the decoder's table (huf_live), Treeless with that code when every symbol
-   of the block has a code and the section comes out smaller.  *ltype: the Literals_Block_Type written (DICT only). */
-template <bool DICT>
+   of the block has a code and the section comes out smaller.  *ltype: the Literals_Block_Type written (DICT only).  USER: as for
+   cze_sequences. */
+template <bool DICT, int USER = 0>
 __device__ static uint32_t cze_literals(const uint8_t* lit, uint32_t nlit, uint8_t* out, uint32_t* hufw, const CzeDict* img, uint32_t huf_live,
                                         uint32_t* ltype) {
     const uint32_t t = threadIdx.x;

@@ -32,6 +32,7 @@
 #include "czstd_pre.hip"
 #include "czstd_wexec.hip"
 #include "czstd_enc.hip"     /* cz_compress_frames_kernel */
+#include "czstd_encsplit.hip" /* cz_compress_plan_kernel, cz_compress_segments_kernel (CZ_COMPRESS_SPLIT) */
 #ifdef CZ_EXP_PAD   /* diagnostic: shifts the code objects behind it by CZ_EXP_PAD x 256 bytes (does the layout of the kernels in the code object matter?) */
 extern "C" __global__ void cz_pad_kernel(uint32_t* p) {
 #pragma unroll
@@ -99,6 +100,10 @@ struct cz_context {
     int last_hip_error = 0, last_hip_line = 0;
     /* batched compression (cz_compress_batch_*): per-workgroup scratch of cz_compress_frames_kernel, allocated by the first call */
     uint8_t* enc_scratch = nullptr; int enc_slots = 0; uint32_t* enc_counter = nullptr; int enc_grid = 0;
+    /* CZ_COMPRESS_SPLIT: the larger per-workgroup scratch of cz_compress_segments_kernel; unit_base (n + 1) and the per-frame state
+       (2 n) in one allocation sized from n; the unit counter */
+    uint8_t* encs_scratch = nullptr; int encs_slots = 0; unsigned long long* encs_plan = nullptr; size_t encs_frames = 0;
+    unsigned long long* encs_counter = nullptr; int encs_grid = 0;
     cze_dict_entry* enc_dicts = nullptr; uint32_t enc_dict_count = 0; int enc_dgrid = 0;   /* cz_context_set_compress_dictionaries */
     /* staging for cz_decode_batch_host */
     void* d_stage = nullptr; size_t d_stage_bytes = 0;
@@ -191,6 +196,9 @@ CZ_EXPORT void cz_context_destroy(cz_context* c) {
     if (c->lit_scratch) (void)hipFree(c->lit_scratch);
     if (c->enc_scratch) (void)hipFree(c->enc_scratch);
     if (c->enc_counter) (void)hipFree(c->enc_counter);
+    if (c->encs_scratch) (void)hipFree(c->encs_scratch);
+    if (c->encs_plan) (void)hipFree(c->encs_plan);
+    if (c->encs_counter) (void)hipFree(c->encs_counter);
     if (c->enc_dicts) (void)hipFree(c->enc_dicts);
     if (c->work_counter) (void)hipFree(c->work_counter);
     if (c->d_stage) (void)hipFree(c->d_stage);
@@ -961,13 +969,52 @@ static int cz_enc_reserve(cz_context* c, int grid) {
     return CZ_OK;
 }
 
+CZ_EXPORT uint64_t cz_compress_split_segment(void) { return CZE_SEG; }
+
+/* CZ_COMPRESS_SPLIT: the plan kernel (units per frame, scanned; the host knows n only), then the persistent segment kernel on as
+   many workgroups as fit; both on the context stream.  Scratch, plan arrays and counter are kept and grown like enc_scratch. */
+static int cz_compress_split_launch(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
+                                    void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
+                                    cz_compress_result* d_results) {
+    if (!c->encs_grid) {
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_segments_kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
+        c->encs_grid = c->num_cu * occ;
+    }
+    const int grid = c->encs_grid;
+    if (c->encs_slots < grid) {
+        if (c->encs_scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->encs_scratch); c->encs_scratch = nullptr; c->encs_slots = 0; }
+        CZ_HIP(c, hipMalloc((void**)&c->encs_scratch, (size_t)grid * CZE_SPLIT_SCRATCH_BYTES));
+        c->encs_slots = grid;
+    }
+    if (c->encs_frames < n) {
+        if (c->encs_plan) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->encs_plan); c->encs_plan = nullptr; c->encs_frames = 0; }
+        CZ_HIP(c, hipMalloc((void**)&c->encs_plan, (3 * n + 1) * sizeof(unsigned long long)));
+        c->encs_frames = n;
+    }
+    if (!c->encs_counter) CZ_HIP(c, hipMalloc((void**)&c->encs_counter, 64));
+    CZ_HIP(c, hipMemsetAsync(c->encs_counter, 0, 8, c->stream));
+    cz_encsplit_args sa; memset(&sa, 0, sizeof sa);
+    sa.a.in_base = (const uint8_t*)d_in_base; sa.a.in_off = d_in_off; sa.a.in_len = d_in_len;
+    sa.a.out_base = (uint8_t*)d_out_base; sa.a.out_off = d_out_off; sa.a.out_cap = d_out_cap; sa.a.results = d_results;
+    sa.a.n = (uint32_t)n; sa.a.flags = flags; sa.a.scratch = c->encs_scratch; sa.a.scratch_stride = CZE_SPLIT_SCRATCH_BYTES;
+    sa.unit_base = c->encs_plan; sa.fstate = c->encs_plan + n + 1; sa.counter = c->encs_counter;
+    hipLaunchKernelGGL(cz_compress_plan_kernel, dim3(1), dim3(CZE_THREADS), 0, c->stream, d_in_len, (uint32_t)n, flags, sa.unit_base, sa.fstate);
+    CZ_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL(cz_compress_segments_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, sa);
+    CZ_HIP(c, hipGetLastError());
+    c->last_grid = grid;
+    return CZ_OK;
+}
+
 CZ_EXPORT int cz_compress_batch_device(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                                        void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                                        cz_compress_result* d_results) {
-    if (!c || (flags & ~CZ_COMPRESS_CHECKSUM) || n > 0xFFFFFFFFull) return CZ_E_INVALID_ARG;
+    if (!c || (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_SPLIT)) || n > 0xFFFFFFFFull) return CZ_E_INVALID_ARG;
     if (n == 0) return CZ_OK;
     if (!d_in_base || !d_in_off || !d_in_len || !d_out_base || !d_out_off || !d_out_cap || !d_results) return CZ_E_INVALID_ARG;
     CZ_HIP(c, hipSetDevice(c->device));
+    if (flags & CZ_COMPRESS_SPLIT) return cz_compress_split_launch(c, d_in_base, d_in_off, d_in_len, n, d_out_base, d_out_off, d_out_cap, flags, d_results);
     if (!c->enc_grid) {                                                 /* workgroups of ~80 KB of LDS: as many as fit on every CU */
         int occ = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_frames_kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
@@ -1023,7 +1070,7 @@ static int cz_compress_staged(cz_context* c, const void* in_base, size_t in_byte
 CZ_EXPORT int cz_compress_batch_host(cz_context* c, const void* in_base, size_t in_bytes, const uint64_t* in_off, const uint64_t* in_len, size_t n,
                                      void* out_base, size_t out_bytes, const uint64_t* out_off, const uint64_t* out_cap, uint32_t flags,
                                      cz_compress_result* results) {
-    if (!c || (flags & ~CZ_COMPRESS_CHECKSUM)) return CZ_E_INVALID_ARG;
+    if (!c || (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_SPLIT))) return CZ_E_INVALID_ARG;
     if (n == 0) return CZ_OK;
     return cz_compress_staged(c, in_base, in_bytes, in_off, in_len, n, out_base, out_bytes, out_off, out_cap, nullptr, results,
         [&](const void* i, const uint64_t* io, const uint64_t* il, void* o, const uint64_t* oo, const uint64_t* oc, const uint32_t*, cz_compress_result* r) {

@@ -442,9 +442,25 @@ int  cz_frame_decoder_decode_from_to(cz_frame_decoder* fd, const uint8_t* src, s
 /* Worst-case frame size for src_len bytes: frame header, a Raw block header per 128 KiB and the optional checksum. */
 uint64_t cz_compress_bound(uint64_t src_len);
 #define CZ_COMPRESS_CHECKSUM 1u     /* append the 4-byte XXH64 content checksum (Content_Checksum_flag) */
+/*
+ * CZ_COMPRESS_SPLIT (cz_compress_batch_device / _host only): an input longer than one segment of
+ * cz_compress_split_segment() bytes (a multiple of 128 KiB) is cut into segments that different workgroups compress at the
+ * same time.  The output is still ONE standard frame: the same header, blocks of at most 128 KiB each Raw, RLE or Compressed,
+ * Last_Block on the final block only, the optional checksum of the whole input; cz_compress_bound still holds.  Matches reach
+ * back into earlier segments (every segment after the first starts from the hash of the input bytes in front of it), and a
+ * later segment writes its first offset explicitly.  The first segment comes out byte for byte as the first segment's worth
+ * of the frame written without the flag.  An input of at most one segment comes out byte for byte as without the flag, and its
+ * result flags do not carry CZ_COMPRESS_SPLIT; a split frame's do.  The bytes depend on the input and the flags alone, never on
+ * the batch, the grid or timing.  A block that does not fit out_cap ends the frame with CZ_E_OUTPUT_TOO_SMALL as without the
+ * flag: bytes_written / bytes_read / blocks cover the whole blocks placed, nothing past bytes_written is touched.
+ * CZ_E_WAIT_EXPIRED: a segment waited for its predecessor beyond a bound of seconds (a fault of the library, not of the input);
+ * the record then reports 0 bytes and the region's contents are unspecified.
+ */
+#define CZ_COMPRESS_SPLIT 4u
+uint64_t cz_compress_split_segment(void);   /* the segment size S in bytes */
 /* One per buffer, written by the device. */
 typedef struct cz_compress_result {
-    int32_t  status;            /* CZ_OK | CZ_E_OUTPUT_TOO_SMALL | CZ_E_INVALID_ARG (an input of 4 GiB - 1 MiB or more) */
+    int32_t  status;            /* CZ_OK | CZ_E_OUTPUT_TOO_SMALL | CZ_E_INVALID_ARG (an input of 4 GiB - 1 MiB or more) | CZ_E_WAIT_EXPIRED */
     uint32_t blocks;            /* blocks written */
     uint64_t bytes_read;        /* input bytes compressed into the blocks written */
     uint64_t bytes_written;     /* frame bytes at out_base + out_off[i]; nothing past them is touched */
@@ -453,7 +469,8 @@ typedef struct cz_compress_result {
 } cz_compress_result;
 /* Compresses in_base[in_off[i] .. +in_len[i]) into out_base[out_off[i] .. +out_cap[i]) for every i < n.  DEVICE pointers
  * (results too); asynchronous on the context stream; no alignment required.  A frame that fails leaves its neighbours and
- * every byte of its own region past bytes_written untouched.  out_cap[i] = cz_compress_bound(in_len[i]) always suffices. */
+ * every byte of its own region past bytes_written untouched.  out_cap[i] = cz_compress_bound(in_len[i]) always suffices.
+ * flags: CZ_COMPRESS_CHECKSUM, CZ_COMPRESS_SPLIT; any other bit is CZ_E_INVALID_ARG. */
 int cz_compress_batch_device(cz_context* ctx, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                              void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                              cz_compress_result* d_results);
@@ -482,7 +499,7 @@ int cz_context_set_compress_dictionaries(cz_context* ctx, const cz_dictionary* c
  * CZ_COMPRESS_NO_DICT (the frame then comes out byte for byte as from cz_compress_batch_device).  Any other index >= k fails that
  * frame alone with CZ_E_INVALID_ARG (nothing written), as does a dictionary content plus input of 4 GiB - 1 MiB or more.
  * d_dict_index (DEVICE, n entries) may be NULL when exactly one dictionary is set: every frame uses it.  flags: CZ_COMPRESS_CHECKSUM,
- * CZ_COMPRESS_NO_DICT_ID. */
+ * CZ_COMPRESS_NO_DICT_ID (CZ_COMPRESS_SPLIT is CZ_E_INVALID_ARG here: split frames take no dictionary). */
 int cz_compress_batch_dict_device(cz_context* ctx, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                                   void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                                   const uint32_t* d_dict_index, cz_compress_result* d_results);

@@ -2,10 +2,15 @@
 
 Run it on the GPU box under a time limit of its own, e.g.
     timeout -k 10 600 python scripts/compress_bench.py --out profiles/compress/bench.json
-Two batches tiled from the golden corpus originals (tests/golden/decode_corpus): 10 000 x 128 KiB and 64 x 2 MiB.  The device
-figure is input bytes over the kernel time (hipEvents around the launch, median of --runs after one warm-up), buffers already in
-HBM.  libzstd (ZSTD_compress, level 1, dlopen'ed) runs the same buffers on --threads threads; it is skipped when the host has no
-libzstd.so.1.  Prints one JSON line per batch and writes them all to --out."""
+Three batches tiled from the golden corpus originals (tests/golden/decode_corpus): 10 000 x 128 KiB, 64 x 2 MiB and 1 x 16 MiB.
+The device figure is input bytes over the kernel time (hipEvents around the launch, median of --runs after one warm-up), buffers
+already in HBM.  libzstd (ZSTD_compress, level 1, dlopen'ed) runs the same buffers on --threads threads; it is skipped when the
+host has no libzstd.so.1 or with --no-libzstd.  Prints one JSON line per batch and writes them all to --out.
+
+--split compresses with CZ_COMPRESS_SPLIT.  --pieces adds the frame bytes of every 128 KiB piece of the 64 x 2 MiB
+batch compressed as a frame of its own, the floor the choice of segment and overlap is judged against.  Builds with another segment
+or overlap (make -C cairo_zstd_amd/csrc exp NAME=s2w128 EXPFLAGS="-DCZE_SEG_BLOCKS=2u -DCZE_OVERLAP=131072u") are picked with
+CAIRO_ZSTD_AMD_LIB; --tag goes into every row to tell them apart."""
 import argparse
 import ctypes
 import json
@@ -32,7 +37,7 @@ def tiled(n, size, seed):
     return [pool[int(s):int(s) + size] for s in starts]
 
 
-def device_run(cz, ctx, stream, bufs, runs):
+def device_run(cz, ctx, stream, bufs, runs, split=False):
     import torch
     dev = torch.device("cuda:0")
     lens = np.array([len(b) for b in bufs], dtype=np.uint64)
@@ -51,7 +56,7 @@ def device_run(cz, ctx, stream, bufs, runs):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
         ctx.compress_batch_device(d_in.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), len(bufs), d_out.data_ptr(),
-                                  desc[2].data_ptr(), desc[3].data_ptr(), d_res.data_ptr())
+                                  desc[2].data_ptr(), desc[3].data_ptr(), d_res.data_ptr(), **(dict(split=True) if split else {}))
         e1.record(stream)
         e1.synchronize()
         if r:
@@ -91,19 +96,30 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--split", action="store_true", help="compress with CZ_COMPRESS_SPLIT")
+    ap.add_argument("--pieces", action="store_true", help="also: the 64 x 2 MiB batch as 1 024 frames of 128 KiB (frame bytes)")
+    ap.add_argument("--no-libzstd", action="store_true")
+    ap.add_argument("--tag", default=None, help="free text copied into every row")
     args = ap.parse_args()
     import torch
     import cairo_zstd_amd as cz
     stream = torch.cuda.Stream()                                        # the context launches on it, the events are recorded on it
     ctx = cz.Context(0, stream.cuda_stream)
     rows = []
-    for name, n, size in (("10000x128KiB", 10000, 128 << 10), ("64x2MiB", 64, 2 << 20)):
+    for name, n, size in (("10000x128KiB", 10000, 128 << 10), ("64x2MiB", 64, 2 << 20), ("1x16MiB", 1, 16 << 20)):
         bufs = tiled(n, size, seed=1)
         nbytes = n * size
-        ms, written = device_run(cz, ctx, stream, bufs, args.runs)
+        ms, written = device_run(cz, ctx, stream, bufs, args.runs, split=args.split)
         row = dict(batch=name, input_bytes=nbytes, device=torch.cuda.get_device_name(0), device_ms=round(ms, 3),
-                   device_gbps=round(nbytes / ms / 1e6, 2), device_ratio=round(nbytes / written, 4))
-        cpu = libzstd_run(bufs, args.threads, args.runs)
+                   device_gbps=round(nbytes / ms / 1e6, 2), device_ratio=round(nbytes / written, 4), frame_bytes=written, split=args.split)
+        if args.split:
+            row["segment"] = cz.compress_split_segment()
+        if args.tag:
+            row["tag"] = args.tag
+        if args.pieces and name == "64x2MiB":
+            pieces = [b[o:o + (128 << 10)] for b in bufs for o in range(0, len(b), 128 << 10)]
+            row["pieces_128KiB_frame_bytes"] = device_run(cz, ctx, stream, pieces, 1)[1]
+        cpu = None if args.no_libzstd else libzstd_run(bufs, args.threads, args.runs)
         if cpu:
             cms, cwritten, ver = cpu
             row.update(libzstd_version=ver, libzstd_level=1, libzstd_threads=args.threads, libzstd_ms=round(cms, 3),
