@@ -25,6 +25,7 @@ assert COMPRESS_RESULT_DTYPE.itemsize == 32
 COMPRESS_CHECKSUM = 1
 COMPRESS_NO_DICT_ID = 2                 # omit the Dictionary_ID field (cz_compress_batch_dict_*)
 COMPRESS_SPLIT = 4                      # cut inputs longer than compress_split_segment() into segments compressed side by side
+COMPRESS_FSE_TABLES = 16                # per-block FSE tables for the sequences where they make the block smaller
 COMPRESS_NO_DICT = 0xFFFFFFFF           # dict_index entry: no dictionary for this buffer
 
 
@@ -46,7 +47,7 @@ class BlockHeader(C.Structure):
 
 def build(force: bool = False) -> str:
     """Compile the library in-tree with hipcc for gfx950 (csrc/Makefile)."""
-    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_enc.hip", "czstd_encsplit.hip", "czstd_types.h", "czstd_dict.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_enc.hip", "czstd_encsplit.hip", "czstd_encfse.hip", "czstd_types.h", "czstd_dict.h")]
     srcs += [os.path.join(_HERE, "..", "include", f) for f in ("cairo_zstd_amd.h", "cairo_zstd_amd_status.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:

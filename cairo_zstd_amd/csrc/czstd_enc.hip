@@ -26,6 +26,10 @@
  * kernels here keep their bodies.  cze_literals and cze_sequences carry a second template parameter only so that it gets copies of
  * its own and these kernels compile to the same code as without it.
  *
+ * CZ_COMPRESS_FSE_TABLES (czstd_encfse.hip, included behind both) writes the sequences of a block with tables made
+ * for that block where they make it smaller.  Its two kernels use this file's helpers up to the literals (USER = 2) and a sequence
+ * writer of their own; the kernels here always use the Predefined tables (the dictionary kernel: or the dictionary's).
+ *
  * Written so that the CPU SIMT emulator of tests/emu (hip/hip_runtime.h) builds it unchanged.  Needs czstd_kernels.hip first
  * (XXH64 rounds, the LL / ML code tables and the Predefined distributions).
  */

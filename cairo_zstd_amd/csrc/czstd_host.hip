@@ -33,6 +33,7 @@
 #include "czstd_wexec.hip"
 #include "czstd_enc.hip"     /* cz_compress_frames_kernel */
 #include "czstd_encsplit.hip" /* cz_compress_plan_kernel, cz_compress_segments_kernel (CZ_COMPRESS_SPLIT) */
+#include "czstd_encfse.hip"   /* cz_compress_frames_fse_kernel, cz_compress_segments_fse_kernel (CZ_COMPRESS_FSE_TABLES) */
 #ifdef CZ_EXP_PAD   /* diagnostic: shifts the code objects behind it by CZ_EXP_PAD x 256 bytes (does the layout of the kernels in the code object matter?) */
 extern "C" __global__ void cz_pad_kernel(uint32_t* p) {
 #pragma unroll
@@ -104,6 +105,10 @@ struct cz_context {
        (2 n) in one allocation sized from n; the unit counter */
     uint8_t* encs_scratch = nullptr; int encs_slots = 0; unsigned long long* encs_plan = nullptr; size_t encs_frames = 0;
     unsigned long long* encs_counter = nullptr; int encs_grid = 0;
+    /* CZ_COMPRESS_FSE_TABLES: the scratch of cz_compress_frames_fse_kernel and of cz_compress_segments_fse_kernel (each that of the
+       kernel it extends plus the codes and chain records), allocated by the first call that sets the flag */
+    uint8_t* encf_scratch = nullptr; int encf_slots = 0; int encf_grid = 0;
+    uint8_t* encfs_scratch = nullptr; int encfs_slots = 0; int encfs_grid = 0;
     cze_dict_entry* enc_dicts = nullptr; uint32_t enc_dict_count = 0; int enc_dgrid = 0;   /* cz_context_set_compress_dictionaries */
     /* staging for cz_decode_batch_host */
     void* d_stage = nullptr; size_t d_stage_bytes = 0;
@@ -199,6 +204,8 @@ CZ_EXPORT void cz_context_destroy(cz_context* c) {
     if (c->encs_scratch) (void)hipFree(c->encs_scratch);
     if (c->encs_plan) (void)hipFree(c->encs_plan);
     if (c->encs_counter) (void)hipFree(c->encs_counter);
+    if (c->encf_scratch) (void)hipFree(c->encf_scratch);
+    if (c->encfs_scratch) (void)hipFree(c->encfs_scratch);
     if (c->enc_dicts) (void)hipFree(c->enc_dicts);
     if (c->work_counter) (void)hipFree(c->work_counter);
     if (c->d_stage) (void)hipFree(c->d_stage);
@@ -976,16 +983,22 @@ CZ_EXPORT uint64_t cz_compress_split_segment(void) { return CZE_SEG; }
 static int cz_compress_split_launch(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                                     void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                                     cz_compress_result* d_results) {
-    if (!c->encs_grid) {
+    const bool fse = flags & CZ_COMPRESS_FSE_TABLES;                    /* the host picks the kernel; each has its own scratch */
+    int& kgrid = fse ? c->encfs_grid : c->encs_grid; int& slots = fse ? c->encfs_slots : c->encs_slots;
+    uint8_t*& scratch = fse ? c->encfs_scratch : c->encs_scratch;
+    const size_t stride = fse ? CZE_FSE_SPLIT_SCRATCH_BYTES : CZE_SPLIT_SCRATCH_BYTES;
+    if (!kgrid) {
         int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_segments_kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
-        c->encs_grid = c->num_cu * occ;
+        const hipError_t e = fse ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_segments_fse_kernel, CZE_THREADS, 0)
+                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_segments_kernel, CZE_THREADS, 0);
+        if (e != hipSuccess || occ <= 0) occ = 1;
+        kgrid = c->num_cu * occ;
     }
-    const int grid = c->encs_grid;
-    if (c->encs_slots < grid) {
-        if (c->encs_scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->encs_scratch); c->encs_scratch = nullptr; c->encs_slots = 0; }
-        CZ_HIP(c, hipMalloc((void**)&c->encs_scratch, (size_t)grid * CZE_SPLIT_SCRATCH_BYTES));
-        c->encs_slots = grid;
+    const int grid = kgrid;
+    if (slots < grid) {
+        if (scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(scratch); scratch = nullptr; slots = 0; }
+        CZ_HIP(c, hipMalloc((void**)&scratch, (size_t)grid * stride));
+        slots = grid;
     }
     if (c->encs_frames < n) {
         if (c->encs_plan) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->encs_plan); c->encs_plan = nullptr; c->encs_frames = 0; }
@@ -997,11 +1010,40 @@ static int cz_compress_split_launch(cz_context* c, const void* d_in_base, const 
     cz_encsplit_args sa; memset(&sa, 0, sizeof sa);
     sa.a.in_base = (const uint8_t*)d_in_base; sa.a.in_off = d_in_off; sa.a.in_len = d_in_len;
     sa.a.out_base = (uint8_t*)d_out_base; sa.a.out_off = d_out_off; sa.a.out_cap = d_out_cap; sa.a.results = d_results;
-    sa.a.n = (uint32_t)n; sa.a.flags = flags; sa.a.scratch = c->encs_scratch; sa.a.scratch_stride = CZE_SPLIT_SCRATCH_BYTES;
+    sa.a.n = (uint32_t)n; sa.a.flags = flags; sa.a.scratch = scratch; sa.a.scratch_stride = stride;
     sa.unit_base = c->encs_plan; sa.fstate = c->encs_plan + n + 1; sa.counter = c->encs_counter;
     hipLaunchKernelGGL(cz_compress_plan_kernel, dim3(1), dim3(CZE_THREADS), 0, c->stream, d_in_len, (uint32_t)n, flags, sa.unit_base, sa.fstate);
     CZ_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL(cz_compress_segments_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, sa);
+    if (fse) hipLaunchKernelGGL(cz_compress_segments_fse_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, sa);
+    else hipLaunchKernelGGL(cz_compress_segments_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, sa);
+    CZ_HIP(c, hipGetLastError());
+    c->last_grid = grid;
+    return CZ_OK;
+}
+
+/* CZ_COMPRESS_FSE_TABLES without CZ_COMPRESS_SPLIT: cz_compress_frames_fse_kernel, launched as cz_compress_frames_kernel is, on a
+   scratch of its own (the chain records make it larger) */
+static int cz_compress_fse_launch(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
+                                  void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
+                                  cz_compress_result* d_results) {
+    if (!c->encf_grid) {
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_frames_fse_kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
+        c->encf_grid = c->num_cu * occ;
+    }
+    const int grid = (size_t)c->encf_grid < n ? c->encf_grid : (int)n;
+    if (c->encf_slots < grid) {
+        if (c->encf_scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->encf_scratch); c->encf_scratch = nullptr; c->encf_slots = 0; }
+        CZ_HIP(c, hipMalloc((void**)&c->encf_scratch, (size_t)grid * CZE_FSE_SCRATCH_BYTES));
+        c->encf_slots = grid;
+    }
+    if (!c->enc_counter) CZ_HIP(c, hipMalloc((void**)&c->enc_counter, 64));
+    CZ_HIP(c, hipMemsetAsync(c->enc_counter, 0, 4, c->stream));
+    cz_enc_args a; memset(&a, 0, sizeof a);
+    a.in_base = (const uint8_t*)d_in_base; a.in_off = d_in_off; a.in_len = d_in_len;
+    a.out_base = (uint8_t*)d_out_base; a.out_off = d_out_off; a.out_cap = d_out_cap; a.results = d_results;
+    a.n = (uint32_t)n; a.flags = flags; a.work_counter = c->enc_counter; a.scratch = c->encf_scratch; a.scratch_stride = CZE_FSE_SCRATCH_BYTES;
+    hipLaunchKernelGGL(cz_compress_frames_fse_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, a);
     CZ_HIP(c, hipGetLastError());
     c->last_grid = grid;
     return CZ_OK;
@@ -1010,11 +1052,12 @@ static int cz_compress_split_launch(cz_context* c, const void* d_in_base, const 
 CZ_EXPORT int cz_compress_batch_device(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                                        void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                                        cz_compress_result* d_results) {
-    if (!c || (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_SPLIT)) || n > 0xFFFFFFFFull) return CZ_E_INVALID_ARG;
+    if (!c || (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_SPLIT | CZ_COMPRESS_FSE_TABLES)) || n > 0xFFFFFFFFull) return CZ_E_INVALID_ARG;
     if (n == 0) return CZ_OK;
     if (!d_in_base || !d_in_off || !d_in_len || !d_out_base || !d_out_off || !d_out_cap || !d_results) return CZ_E_INVALID_ARG;
     CZ_HIP(c, hipSetDevice(c->device));
     if (flags & CZ_COMPRESS_SPLIT) return cz_compress_split_launch(c, d_in_base, d_in_off, d_in_len, n, d_out_base, d_out_off, d_out_cap, flags, d_results);
+    if (flags & CZ_COMPRESS_FSE_TABLES) return cz_compress_fse_launch(c, d_in_base, d_in_off, d_in_len, n, d_out_base, d_out_off, d_out_cap, flags, d_results);
     if (!c->enc_grid) {                                                 /* workgroups of ~80 KB of LDS: as many as fit on every CU */
         int occ = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_frames_kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
@@ -1070,7 +1113,7 @@ static int cz_compress_staged(cz_context* c, const void* in_base, size_t in_byte
 CZ_EXPORT int cz_compress_batch_host(cz_context* c, const void* in_base, size_t in_bytes, const uint64_t* in_off, const uint64_t* in_len, size_t n,
                                      void* out_base, size_t out_bytes, const uint64_t* out_off, const uint64_t* out_cap, uint32_t flags,
                                      cz_compress_result* results) {
-    if (!c || (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_SPLIT))) return CZ_E_INVALID_ARG;
+    if (!c || (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_SPLIT | CZ_COMPRESS_FSE_TABLES))) return CZ_E_INVALID_ARG;
     if (n == 0) return CZ_OK;
     return cz_compress_staged(c, in_base, in_bytes, in_off, in_len, n, out_base, out_bytes, out_off, out_cap, nullptr, results,
         [&](const void* i, const uint64_t* io, const uint64_t* il, void* o, const uint64_t* oo, const uint64_t* oc, const uint32_t*, cz_compress_result* r) {

@@ -436,8 +436,9 @@ int  cz_frame_decoder_decode_from_to(cz_frame_decoder* fd, const uint8_t* src, s
  * Frame format: magic; Frame_Content_Size always written; Single_Segment when the input is at most 1 MiB, otherwise a
  * 1 MiB window (no offset exceeds it); no Dictionary_ID.  Blocks of at most 128 KiB, each Raw, RLE or Compressed,
  * whichever is smallest (an empty input: one empty last Raw block).  Literals Raw, RLE or Huffman (one stream below
- * 1 KiB of literals, four from 1 KiB, codes of at most 11 bits); sequences with the Predefined tables.  A frame's bytes
- * depend on its input bytes and `flags` alone, never on the batch it was compressed in.
+ * 1 KiB of literals, four from 1 KiB, codes of at most 11 bits); sequences with the Predefined tables, or with
+ * CZ_COMPRESS_FSE_TABLES the block's own.  A frame's bytes depend on its input bytes and `flags` alone, never on the batch
+ * it was compressed in.
  */
 /* Worst-case frame size for src_len bytes: frame header, a Raw block header per 128 KiB and the optional checksum. */
 uint64_t cz_compress_bound(uint64_t src_len);
@@ -458,6 +459,17 @@ uint64_t cz_compress_bound(uint64_t src_len);
  */
 #define CZ_COMPRESS_SPLIT 4u
 uint64_t cz_compress_split_segment(void);   /* the segment size S in bytes */
+/*
+ * CZ_COMPRESS_FSE_TABLES (cz_compress_batch_device / _host only, alone or with the two flags above): in every
+ * Compressed block each of the literal-length, offset and match-length codes is written with Predefined_Mode, RLE_Mode (every
+ * sequence of the block has the same code) or FSE_Compressed_Mode with a table made from the block's own histogram, whichever
+ * makes the block smallest, compared by exact size (ties: Predefined, then RLE).  Repeat_Mode of an earlier table of the frame is
+ * never written.  Everything else about the frame is as without the flag, so a frame without sequences comes out byte for byte
+ * the same; cz_compress_bound still holds.  The result flags carry the bit whenever it was requested.  The value is 16: 8 stays an
+ * unknown bit.  CZ_E_INVALID_ARG in cz_compress_batch_dict_*: dictionary frames use the dictionary's tables (Repeat) or the
+ * Predefined ones, and mixing a dictionary's tables with the frame's own is left for later.
+ */
+#define CZ_COMPRESS_FSE_TABLES 16u
 /* One per buffer, written by the device. */
 typedef struct cz_compress_result {
     int32_t  status;            /* CZ_OK | CZ_E_OUTPUT_TOO_SMALL | CZ_E_INVALID_ARG (an input of 4 GiB - 1 MiB or more) | CZ_E_WAIT_EXPIRED */
@@ -470,7 +482,7 @@ typedef struct cz_compress_result {
 /* Compresses in_base[in_off[i] .. +in_len[i]) into out_base[out_off[i] .. +out_cap[i]) for every i < n.  DEVICE pointers
  * (results too); asynchronous on the context stream; no alignment required.  A frame that fails leaves its neighbours and
  * every byte of its own region past bytes_written untouched.  out_cap[i] = cz_compress_bound(in_len[i]) always suffices.
- * flags: CZ_COMPRESS_CHECKSUM, CZ_COMPRESS_SPLIT; any other bit is CZ_E_INVALID_ARG. */
+ * flags: CZ_COMPRESS_CHECKSUM, CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES; any other bit is CZ_E_INVALID_ARG. */
 int cz_compress_batch_device(cz_context* ctx, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                              void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                              cz_compress_result* d_results);
@@ -499,7 +511,8 @@ int cz_context_set_compress_dictionaries(cz_context* ctx, const cz_dictionary* c
  * CZ_COMPRESS_NO_DICT (the frame then comes out byte for byte as from cz_compress_batch_device).  Any other index >= k fails that
  * frame alone with CZ_E_INVALID_ARG (nothing written), as does a dictionary content plus input of 4 GiB - 1 MiB or more.
  * d_dict_index (DEVICE, n entries) may be NULL when exactly one dictionary is set: every frame uses it.  flags: CZ_COMPRESS_CHECKSUM,
- * CZ_COMPRESS_NO_DICT_ID (CZ_COMPRESS_SPLIT is CZ_E_INVALID_ARG here: split frames take no dictionary). */
+ * CZ_COMPRESS_NO_DICT_ID (CZ_COMPRESS_SPLIT and CZ_COMPRESS_FSE_TABLES are CZ_E_INVALID_ARG here: split frames take no dictionary,
+ * and dictionary frames no tables of their own). */
 int cz_compress_batch_dict_device(cz_context* ctx, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                                   void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                                   const uint32_t* d_dict_index, cz_compress_result* d_results);

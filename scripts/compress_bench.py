@@ -10,7 +10,11 @@ host has no libzstd.so.1 or with --no-libzstd.  Prints one JSON line per batch a
 --split compresses with CZ_COMPRESS_SPLIT.  --pieces adds the frame bytes of every 128 KiB piece of the 64 x 2 MiB
 batch compressed as a frame of its own, the floor the choice of segment and overlap is judged against.  Builds with another segment
 or overlap (make -C cairo_zstd_amd/csrc exp NAME=s2w128 EXPFLAGS="-DCZE_SEG_BLOCKS=2u -DCZE_OVERLAP=131072u") are picked with
-CAIRO_ZSTD_AMD_LIB; --tag goes into every row to tell them apart."""
+CAIRO_ZSTD_AMD_LIB; --tag goes into every row to tell them apart.
+
+--fse-tables measures CZ_COMPRESS_FSE_TABLES: every batch unsplit and split, each without and with the flag in
+the same session, and the frame bytes of the 69 corpus originals without and with it; --out defaults to
+profiles/compress/fse_bench.json."""
 import argparse
 import ctypes
 import json
@@ -37,7 +41,7 @@ def tiled(n, size, seed):
     return [pool[int(s):int(s) + size] for s in starts]
 
 
-def device_run(cz, ctx, stream, bufs, runs, split=False):
+def device_run(cz, ctx, stream, bufs, runs, split=False, fse=False):
     import torch
     dev = torch.device("cuda:0")
     lens = np.array([len(b) for b in bufs], dtype=np.uint64)
@@ -56,7 +60,8 @@ def device_run(cz, ctx, stream, bufs, runs, split=False):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
         ctx.compress_batch_device(d_in.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), len(bufs), d_out.data_ptr(),
-                                  desc[2].data_ptr(), desc[3].data_ptr(), d_res.data_ptr(), **(dict(split=True) if split else {}))
+                                  desc[2].data_ptr(), desc[3].data_ptr(), d_res.data_ptr(), **(dict(split=True) if split else {}),
+                                  **(dict(fse_tables=True) if fse else {}))
         e1.record(stream)
         e1.synchronize()
         if r:
@@ -98,6 +103,7 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--split", action="store_true", help="compress with CZ_COMPRESS_SPLIT")
     ap.add_argument("--pieces", action="store_true", help="also: the 64 x 2 MiB batch as 1 024 frames of 128 KiB (frame bytes)")
+    ap.add_argument("--fse-tables", action="store_true", help="measure CZ_COMPRESS_FSE_TABLES next to the same launches without it")
     ap.add_argument("--no-libzstd", action="store_true")
     ap.add_argument("--tag", default=None, help="free text copied into every row")
     args = ap.parse_args()
@@ -106,26 +112,39 @@ def main():
     stream = torch.cuda.Stream()                                        # the context launches on it, the events are recorded on it
     ctx = cz.Context(0, stream.cuda_stream)
     rows = []
+    if args.fse_tables:
+        args.out = args.out or os.path.join(ROOT, "profiles", "compress", "fse_bench.json")
+        d = os.path.join(ROOT, "tests", "golden", "decode_corpus")
+        originals = [open(os.path.join(d, n), "rb").read() for n in sorted(os.listdir(d)) if not n.endswith(".zst")]
+        row = dict(batch="corpus originals", count=len(originals), input_bytes=sum(map(len, originals)))
+        for key, fse in (("frame_bytes", False), ("frame_bytes_fse_tables", True)):
+            row[key] = sum(len(fr) for _, fr in cz.compress_batch_host(originals, ctx, fse_tables=fse))
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    variants = [(s, f) for s in (False, True) for f in (False, True)] if args.fse_tables else [(args.split, False)]
     for name, n, size in (("10000x128KiB", 10000, 128 << 10), ("64x2MiB", 64, 2 << 20), ("1x16MiB", 1, 16 << 20)):
         bufs = tiled(n, size, seed=1)
         nbytes = n * size
-        ms, written = device_run(cz, ctx, stream, bufs, args.runs, split=args.split)
-        row = dict(batch=name, input_bytes=nbytes, device=torch.cuda.get_device_name(0), device_ms=round(ms, 3),
-                   device_gbps=round(nbytes / ms / 1e6, 2), device_ratio=round(nbytes / written, 4), frame_bytes=written, split=args.split)
-        if args.split:
-            row["segment"] = cz.compress_split_segment()
-        if args.tag:
-            row["tag"] = args.tag
-        if args.pieces and name == "64x2MiB":
-            pieces = [b[o:o + (128 << 10)] for b in bufs for o in range(0, len(b), 128 << 10)]
-            row["pieces_128KiB_frame_bytes"] = device_run(cz, ctx, stream, pieces, 1)[1]
-        cpu = None if args.no_libzstd else libzstd_run(bufs, args.threads, args.runs)
-        if cpu:
-            cms, cwritten, ver = cpu
-            row.update(libzstd_version=ver, libzstd_level=1, libzstd_threads=args.threads, libzstd_ms=round(cms, 3),
-                       libzstd_gbps=round(nbytes / cms / 1e6, 2), libzstd_ratio=round(nbytes / cwritten, 4))
-        print(json.dumps(row), flush=True)
-        rows.append(row)
+        for split, fse in variants:
+            ms, written = device_run(cz, ctx, stream, bufs, args.runs, split=split, fse=fse)
+            row = dict(batch=name, input_bytes=nbytes, device=torch.cuda.get_device_name(0), device_ms=round(ms, 3),
+                       device_gbps=round(nbytes / ms / 1e6, 2), device_ratio=round(nbytes / written, 4), frame_bytes=written, split=split)
+            if args.fse_tables:
+                row["fse_tables"] = fse
+            if split:
+                row["segment"] = cz.compress_split_segment()
+            if args.tag:
+                row["tag"] = args.tag
+            if args.pieces and name == "64x2MiB":
+                pieces = [b[o:o + (128 << 10)] for b in bufs for o in range(0, len(b), 128 << 10)]
+                row["pieces_128KiB_frame_bytes"] = device_run(cz, ctx, stream, pieces, 1)[1]
+            cpu = None if args.no_libzstd or (split, fse) != variants[0] else libzstd_run(bufs, args.threads, args.runs)
+            if cpu:
+                cms, cwritten, ver = cpu
+                row.update(libzstd_version=ver, libzstd_level=1, libzstd_threads=args.threads, libzstd_ms=round(cms, 3),
+                           libzstd_gbps=round(nbytes / cms / 1e6, 2), libzstd_ratio=round(nbytes / cwritten, 4))
+            print(json.dumps(row), flush=True)
+            rows.append(row)
     ctx.close()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
