@@ -178,27 +178,89 @@ __device__ static inline uint4 czc_load16(uintptr_t a, uintptr_t S, uintptr_t E)
  * old_lo - new_lo <= 256).  Every lane of a quad passes the same arguments.  The 256 bytes below the
  * ring are always on their way or already in registers (czc_prefetch, issued right after the previous
  * top-up), so a top-up is sixteen LDS writes per slot and no wait for global memory; the caller tops up
- * EVERY slot whenever any slot runs low. */
+ * EVERY slot whenever any slot runs low.
+ *
+ * On the device the prefetched pieces live in a[0:15], registers the compiler never allocates in this kernel (it spills
+ * nothing), and are loaded and read by inline asm: as C++ values they were carried round the main loop, the compiler copied
+ * them at the loop header, and its s_waitcnt vmcnt(0) in front of the copies waited — once per group of steps, top-up or not —
+ * for every record store of the asm group, which its counter does not see (profiles/chain_loop/NOTES.md).  A top-up now
+ * waits for the prefetch loads alone: vector-memory operations of a wave retire in issue order, so with `since` record
+ * stores issued behind the youngest prefetch load, s_waitcnt vmcnt(since) is enough (czc_pre_take).  The host pass and the
+ * CPU emulator keep the pieces in CzcPre. */
 #define CZC_PF (16 / CZC_LPS)
+#ifdef CZC_EXP_NOSTORE
+#define CZC_GROUP_STORES 0u                 /* (diagnostic build without the record store: nothing to count, every top-up waits for vmcnt(0)) */
+#else
+#define CZC_GROUP_STORES (CZC_STEPS / 2u)   /* vector-memory operations one asm group issues: a 16-byte record store per two steps, by every lane */
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+struct CzcPre { };
+#define CZC_PRE_PIECE(A0, A1, A2, A3, has, adr) do { \
+        if (has) { \
+            if ((adr) >= Sk && (adr) + 16 <= Ek) \
+                asm volatile("global_load_dwordx4 a[" #A0 ":" #A3 "], %0, off" :: "v"((CZ_GLOBAL const void*)(adr)) : "memory", "a" #A0, "a" #A1, "a" #A2, "a" #A3); \
+            else if ((adr) + 16 <= Sk || (adr) >= Ek)   /* outside the stream: zeros (below a stream's start near the end of every block) */ \
+                asm volatile("v_accvgpr_write_b32 a" #A0 ", 0\nv_accvgpr_write_b32 a" #A1 ", 0\nv_accvgpr_write_b32 a" #A2 ", 0\nv_accvgpr_write_b32 a" #A3 ", 0" \
+                             ::: "memory", "a" #A0, "a" #A1, "a" #A2, "a" #A3); \
+            else {                                      /* an end of the stream: put together by the lane (twice per block) */ \
+                const uint4 v_ = czc_load16(adr, Sk, Ek); \
+                asm volatile("v_accvgpr_write_b32 a" #A0 ", %0\nv_accvgpr_write_b32 a" #A1 ", %1\nv_accvgpr_write_b32 a" #A2 ", %2\nv_accvgpr_write_b32 a" #A3 ", %3" \
+                             :: "v"(v_.x), "v"(v_.y), "v"(v_.z), "v"(v_.w) : "memory", "a" #A0, "a" #A1, "a" #A2, "a" #A3); \
+            } \
+        } \
+    } while (0)
+/* A lane WRITES the pieces it does not load: no older load may be on its way to the same registers then.  There is none behind a
+   czc_commit (czc_pre_take has waited for every prefetch load of the wave); a slot that takes a new block never committed what it
+   prefetched last for the old one: czc_pre_settle first. */
+__device__ static inline void czc_pre_settle() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+__device__ static inline void czc_prefetch(CzcPre&, int has_slot, intptr_t lo, uintptr_t Sk, uintptr_t Ek) {
+    const uintptr_t a0 = (uintptr_t)lo - 16u * (((uint32_t)LANE & 3u) + 1);
+    static_assert(CZC_PF == 4 && CZC_LPS == 4, "a[0:15], pieces 64 bytes apart");
+    CZC_PRE_PIECE(0, 1, 2, 3, has_slot, a0);
+    CZC_PRE_PIECE(4, 5, 6, 7, has_slot, a0 - 64);
+    CZC_PRE_PIECE(8, 9, 10, 11, has_slot, a0 - 128);
+    CZC_PRE_PIECE(12, 13, 14, 15, has_slot, a0 - 192);
+}
+/* The prefetched pieces, once their loads have landed.  `since` (uniform): vector-memory operations this wave has issued
+   behind its youngest prefetch load, at least; the counter holds 6 bits, so beyond 48 the wait is for 48. */
+__device__ static inline void czc_pre_take(const CzcPre&, uint32_t since, uint4* v) {
+    if (since >= 48u) asm volatile("s_waitcnt vmcnt(48)" ::: "memory");
+    else if (since >= 32u) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
+    else if (since >= 16u) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("v_accvgpr_read_b32 %0, a0\nv_accvgpr_read_b32 %1, a1\nv_accvgpr_read_b32 %2, a2\nv_accvgpr_read_b32 %3, a3\n"
+                 "v_accvgpr_read_b32 %4, a4\nv_accvgpr_read_b32 %5, a5\nv_accvgpr_read_b32 %6, a6\nv_accvgpr_read_b32 %7, a7\n"
+                 "v_accvgpr_read_b32 %8, a8\nv_accvgpr_read_b32 %9, a9\nv_accvgpr_read_b32 %10, a10\nv_accvgpr_read_b32 %11, a11\n"
+                 "v_accvgpr_read_b32 %12, a12\nv_accvgpr_read_b32 %13, a13\nv_accvgpr_read_b32 %14, a14\nv_accvgpr_read_b32 %15, a15"
+                 : "=v"(v[0].x), "=v"(v[0].y), "=v"(v[0].z), "=v"(v[0].w), "=v"(v[1].x), "=v"(v[1].y), "=v"(v[1].z), "=v"(v[1].w),
+                   "=v"(v[2].x), "=v"(v[2].y), "=v"(v[2].z), "=v"(v[2].w), "=v"(v[3].x), "=v"(v[3].y), "=v"(v[3].z), "=v"(v[3].w)
+                 :: "memory");
+}
+#else
 struct CzcPre { uint4 v[CZC_PF]; };
 __device__ static inline void czc_prefetch(CzcPre& pre, int has_slot, intptr_t lo, uintptr_t Sk, uintptr_t Ek) {
     const uint32_t j = (uint32_t)LANE & 3u;
-#pragma unroll
     for (uint32_t r = 0; r < CZC_PF; r++) {
         const uint32_t c = j + r * CZC_LPS;
         if (has_slot) pre.v[r] = czc_load16((uintptr_t)lo - 16u * (c + 1), Sk, Ek);
     }
 }
-__device__ static inline void czc_commit(CzChainSlot& sk, int has_slot, intptr_t old_lo, intptr_t new_lo, const CzcPre& pre) {
+__device__ static inline void czc_pre_settle() { }
+__device__ static inline void czc_pre_take(const CzcPre& pre, uint32_t, uint4* v) { for (uint32_t r = 0; r < CZC_PF; r++) v[r] = pre.v[r]; }
+#endif
+/* old_lo, new_lo: relative to the slot's ring base (a multiple of the ring size: the place in the ring is the same) */
+__device__ static inline void czc_commit(CzChainSlot& sk, int has_slot, int32_t old_lo, int32_t new_lo, const CzcPre& pre, uint32_t since) {
     const uint32_t j = (uint32_t)LANE & 3u;
     const uint32_t cnt = has_slot ? (uint32_t)(old_lo - new_lo) >> 4 : 0u;
+    uint4 v[CZC_PF];
+    czc_pre_take(pre, since, v);
 #pragma unroll
     for (uint32_t r = 0; r < CZC_PF; r++) {
         const uint32_t c = j + r * CZC_LPS;
         if (c < cnt) {
-            const uint32_t slot = (uint32_t)(((uintptr_t)old_lo - 16u * (c + 1)) & (CZC_RING - 1));
-            *(uint4*)&sk.ring[slot] = pre.v[r];
-            if (slot == CZC_RING - 16) { *(uint32_t*)&sk.mirror[4] = pre.v[r].y; *(uint32_t*)&sk.mirror[8] = pre.v[r].z; *(uint32_t*)&sk.mirror[12] = pre.v[r].w; }
+            const uint32_t slot = ((uint32_t)old_lo - 16u * (c + 1)) & (CZC_RING - 1);
+            *(uint4*)&sk.ring[slot] = v[r];
+            if (slot == CZC_RING - 16) { *(uint32_t*)&sk.mirror[4] = v[r].y; *(uint32_t*)&sk.mirror[8] = v[r].z; *(uint32_t*)&sk.mirror[12] = v[r].w; }
         }
     }
 }
@@ -545,6 +607,17 @@ __device__ static inline void czc_group_asm_wide(CzcLane& c, const CzcRole& ro, 
 #else
 #define CZC_PROF_ACC(i) do { } while (0)
 #define CZC_PROF_CNT(i) do { } while (0)
+#endif
+/* does any lane say so?  (uniform.)  Callers pass ONE comparison: its lane mask is then the answer; for a conjunction the compiler
+   writes the flag into a register (v_cndmask) and compares it again.  Hence the values of a slot without a chain are kept where
+   no comparison of the main loop holds for them: CZC_LO_DEAD, CZC_NSEQ_DEAD with done == 0, wide == 0, the idle table entry
+   (no extra bits: c.slow stays 0, as in lane 3 of every quad), and `exhausted` set in the lanes that own no slot. */
+#define CZC_LO_DEAD (-(1 << 30))
+#define CZC_NSEQ_DEAD 0xFFFFFFFFu
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ static inline bool czc_any(bool b) { return __builtin_amdgcn_ballot_w64(b) != 0; }
+#else
+__device__ static inline bool czc_any(bool b) { return __ballot(b ? 1 : 0) != 0; }
 #endif
 /* value held by lane 0 of this lane's quad (every lane takes part) */
 __device__ static inline uint32_t czc_q0(uint32_t v) { return (uint32_t)__shfl((int)v, LANE & ~3); }
@@ -982,18 +1055,24 @@ extern "C" __global__ void __launch_bounds__(CZ_WG_THREADS, 1) cz_chain_kernel(c
     const int publish = a.chain_part == 1u;
     if (list_lo >= list_hi) { if (LANE == 0) atomicAdd(&a.scan_ctl[205], 1u); return; }   /* nothing for this launch: its waves leave at once */
     /* per slot (the same values in the four lanes of its quad, except where noted) */
-    int chain_live = 0, wide = 0, exhausted = 0;                        /* exhausted: owner lanes */
-    uint32_t qnseq = 0, done = 0, sbits = 0;
-    uintptr_t S = 0, E = 0; intptr_t ring_base = 0, loaded_lo = 0;
+    int chain_live = 0, wide = 0, exhausted = owner ? 0 : 1;            /* exhausted: owner lanes (set in all others) */
+    uint32_t qnseq = CZC_NSEQ_DEAD, done = 0, sbits = 0;
+    uintptr_t S = 0, E = 0; intptr_t ring_base = 0;
+    int32_t lo_rel = CZC_LO_DEAD;                                               /* the ring holds the stream from ring_base + lo_rel on */
     CZ_GLOBAL uint64_t* rec = nullptr;
+    /* per lane: where the next asm group stores its records (lanes 0..2 of a live quad: the chain's; every other lane: the sink),
+       and how far a group moves that */
+    CZ_GLOBAL uint64_t* const sink = (CZ_GLOBAL uint64_t*)(a.chain_arena + 8);
+    CZ_GLOBAL uint64_t* rp = sink; uint32_t rp_step = 0;
+    (void)rp;
     /* owner lanes: the block in hand */
     uint32_t o_frame = 0, o_nseq = 0, o_mapflags = 0, o_bitoff = 0, o_bad0 = 0; uint64_t o_hdr = 0; int o_have = 0, o_pub = 0;
     CzcLane c; c.E = (uint32_t)CZC_E16_IDLE << 16; c.S = 0; c.u = 0; c.ph = 0; c.w0 = c.w1 = c.w2 = 0; c.slow = 0;
-    CzcPre pre;
-    for (uint32_t r = 0; r < CZC_PF; r++) pre.v[r] = uint4{0, 0, 0, 0};
+    CzcPre pre = {};
+    uint32_t since = 0;                                                 /* uniform: record stores issued behind the youngest prefetch load (czc_pre_take) */
     for (;;) {
         /* ---- slots without a block take the next one of the list */
-        if (__ballot(owner && !o_have && !exhausted)) {
+        if (czc_any((o_have | exhausted) == 0)) {
             cz_gcptr blk = nullptr; uint32_t bsize = 0, sbody = 0, modes = 0; uint32_t def[3] = {0, 0, 0};
             int got = 0;
             if (owner && !o_have && !exhausted) {
@@ -1124,13 +1203,15 @@ extern "C" __global__ void __launch_bounds__(CZ_WG_THREADS, 1) cz_chain_kernel(c
                 S = gblk + gbitoff; E = gblk + gbsize; qnseq = gn; done = 0; wide = 0;
                 sbits = (uint32_t)(S & (CZC_RING - 1)) * 8u;
                 ring_base = (intptr_t)(S & ~(uintptr_t)(CZC_RING - 1));   /* ring-space bit u <-> byte ring_base + (u >> 3) */
-                const intptr_t hi = (intptr_t)((E + 15) & ~(uintptr_t)15);
-                loaded_lo = hi - 256;
-                czc_prefetch(pre, 1, hi, S, E);
-                czc_commit(sl, 1, hi, loaded_lo, pre);
+                lo_rel = (int32_t)((intptr_t)((E + 15) & ~(uintptr_t)15) - ring_base) - 256;
             }
+            /* (every lane takes the pieces: the wait in front of them is the wave's) */
+            czc_pre_settle();
+            czc_prefetch(pre, qgot, ring_base + lo_rel + 256, S, E);
+            czc_commit(sl, qgot, lo_rel + 256, lo_rel, pre, 0u);
             CZC_SYNC();
-            if (qgot) czc_prefetch(pre, 1, loaded_lo, S, E);               /* the next 256 bytes: in registers long before they are needed */
+            czc_prefetch(pre, qgot, ring_base + lo_rel, S, E);             /* the next 256 bytes: in registers long before they are needed */
+            since = 0;
             /* initial states (owner), handed to the lanes of the quad */
             int32_t u0 = 0; uint32_t st_ll = 0, st_of = 0, st_ml = 0;
             if (got) {
@@ -1161,27 +1242,28 @@ extern "C" __global__ void __launch_bounds__(CZ_WG_THREADS, 1) cz_chain_kernel(c
                     c.E = (uint32_t)ro.tb[c.S] << 16;
                     czc_ring_words(c, ro);
                     rec = (CZ_GLOBAL uint64_t*)(a.chain_arena + qh + 4 + CZC_MAP_WORDS);
+                    if (ql < 3) { rp = rec; rp_step = CZC_STEPS; }
                     chain_live = 1;
                 }
             }
             CZC_PROF_ACC(1);
         }
-        if (!__ballot(chain_live)) { if (!__ballot(owner && !exhausted)) break; continue; }
+        if (!czc_any(chain_live != 0)) { if (!czc_any(exhausted == 0)) break; continue; }
         /* ---- keep CZC_NEED bytes below every live cursor staged; when one slot runs low, all top up */
         {
             const int32_t uq = (int32_t)czc_qp<CZC_QP(0, 0, 0, 0)>((uint32_t)c.u);   /* lane 3 of a quad does not follow the cursor */
-            const intptr_t curb = ring_base + ((uq > 0 ? uq - 1 : 0) >> 3);    /* byte that holds the next unread bit */
-            const int need = chain_live && (curb - (intptr_t)CZC_NEED < loaded_lo);
-            if (__ballot(need)) {
+            const int32_t cur = ((uq > 0 ? uq : 1) - 1) >> 3;                  /* byte that holds the next unread bit, from ring_base */
+            if (czc_any(cur - (int32_t)CZC_NEED < lo_rel)) {
                 /* lowest start whose 512 bytes still cover the word at the cursor */
-                intptr_t new_lo = chain_live ? ((curb - (intptr_t)(CZC_RING - 4) + 15) & ~(intptr_t)15) : loaded_lo;
-                if (new_lo > loaded_lo) new_lo = loaded_lo;
-                if (new_lo < loaded_lo - 256) new_lo = loaded_lo - 256;      /* czc_commit moves at most 16 pieces */
+                int32_t new_lo = chain_live ? ((cur - (int32_t)(CZC_RING - 4) + 15) & ~15) : lo_rel;
+                if (new_lo > lo_rel) new_lo = lo_rel;
+                if (new_lo < lo_rel - 256) new_lo = lo_rel - 256;            /* czc_commit moves at most 16 pieces */
                 CZC_SYNC();
-                czc_commit(sl, chain_live, loaded_lo, new_lo, pre);
-                loaded_lo = new_lo;
+                czc_commit(sl, chain_live, lo_rel, new_lo, pre, since);
+                lo_rel = new_lo;
                 CZC_SYNC();
-                czc_prefetch(pre, chain_live, loaded_lo, S, E);
+                czc_prefetch(pre, chain_live, ring_base + lo_rel, S, E);
+                since = 0;
                 if (chain_live) czc_ring_words(c, ro);                    /* the words under the cursor may just have arrived */
                 CZC_PROF_ACC(2); CZC_PROF_CNT(5);
             }
@@ -1191,25 +1273,31 @@ extern "C" __global__ void __launch_bounds__(CZ_WG_THREADS, 1) cz_chain_kernel(c
             /* uniform choice of the loop flavour: the scheduled asm group of CZC_STEPS steps unless a chain is near its end;
                a block that met a sequence of more than 32 extra bits goes on with the wide asm group (the narrow one is redone) */
             const uint32_t left = qnseq - done;
-            const int tail = __ballot(chain_live && left <= CZC_STEPS) != 0;
+            const bool tail = czc_any(left <= CZC_STEPS);
             int ran_asm = 0;
             (void)tail; (void)wide;
 #if defined(__HIP_DEVICE_COMPILE__)
             if (!tail && !(a.debug_flags & CZ_DEBUG_CHAIN_CPP_STEP)) {
-                CZ_GLOBAL uint64_t* rp = chain_live && ql < 3 ? rec + done : (CZ_GLOBAL uint64_t*)(a.chain_arena + 8);
-                if (!__ballot(chain_live && wide)) {
-                    const CzcLane sv = c;
+                bool any_wide = czc_any(wide != 0);
+                if (!any_wide) {
+                    const uint32_t sv_E = c.E, sv_S = c.S; const int32_t sv_u = c.u;   /* what a redo starts from (the ring words are read again) */
                     c.slow = 0;
 #ifdef CZC_EXP_OLD_STEP
                     czc_group_asm(c, ro, rp);
 #else
                     czc_group_asm2(c, ro, rp);
 #endif
-                    const int hit = chain_live && ql < 3 && c.slow > 32;
-                    if (__ballot(hit)) { wide |= (int)czc_q0((uint32_t)hit); c = sv; }   /* redo this group wide; the slots that met a wide sequence stay wide for their block */
+                    since += CZC_GROUP_STORES;
+                    if (czc_any(c.slow > 32)) {                         /* redo this group wide; the slots that met a wide sequence stay wide for their block */
+                        const int hit = chain_live && ql < 3 && c.slow > 32;
+                        wide |= (int)czc_q0((uint32_t)hit);
+                        c.E = sv_E; c.S = sv_S; c.u = sv_u; czc_ring_words(c, ro);
+                        any_wide = true;
+                    }
                 }
-                if (__ballot(chain_live && wide)) czc_group_asm_wide(c, ro, rp);
+                if (any_wide) { czc_group_asm_wide(c, ro, rp); since += CZC_GROUP_STORES; }   /* (the C++ groups below store per live lane: not counted, the wait is only longer) */
                 if (chain_live) done += CZC_STEPS;
+                rp += rp_step;
                 ran_asm = 1;
             }
 #endif
@@ -1217,11 +1305,12 @@ extern "C" __global__ void __launch_bounds__(CZ_WG_THREADS, 1) cz_chain_kernel(c
                 const uint32_t steps = !chain_live ? 0u : (left < CZC_WIDE_STEPS ? left : CZC_WIDE_STEPS);
                 for (uint32_t i = 0; i < CZC_WIDE_STEPS; i++) czc_step(c, ro, rec + done + i, i < steps, done + i + 1 == qnseq, ql == 0);
                 done += steps;
+                if (rp_step) rp += steps;                                  /* rp == rec + done in the lanes that store a live chain's records */
             }
             CZC_PROF_ACC(3); CZC_PROF_CNT(6);
         }
         /* ---- finished chains: finalize the block (owner) and free the slot */
-        if (__ballot(chain_live && done >= qnseq)) {
+        if (czc_any(done >= qnseq)) {
             const int fin = chain_live && done >= qnseq;
             int fbad = 0;
             if (fin && owner) {
@@ -1238,7 +1327,7 @@ extern "C" __global__ void __launch_bounds__(CZ_WG_THREADS, 1) cz_chain_kernel(c
                 CZ_RELEASE_AGENT();
                 if (fin && owner && o_pub) CZ_ST_AGENT(&a.chain_arena[o_hdr + 3], (uint64_t)(fbad ? 2 : 1));
             }
-            if (fin) { chain_live = 0; wide = 0; ro.tb = cs.idle; c.S = 0; c.E = (uint32_t)CZC_E16_IDLE << 16; }
+            if (fin) { chain_live = 0; wide = 0; ro.tb = cs.idle; c.S = 0; c.E = (uint32_t)CZC_E16_IDLE << 16; rp = sink; rp_step = 0; qnseq = CZC_NSEQ_DEAD; done = 0; lo_rel = CZC_LO_DEAD; }
             CZC_PROF_ACC(4);
         }
     }
