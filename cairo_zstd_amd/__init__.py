@@ -8,6 +8,7 @@ Python here is a thin mirror over the C ABI (include/cairo_zstd_amd.h, libcairo_
   * compress / compress_batch_host / Context.compress_batch_device : batched compression on the device (split=True: a large
     buffer on many workgroups, still one frame; fse_tables=True: per-block FSE tables for the sequences)
   * compress_batch_host_dict / Context.compress_batch_dict_device : the same with dictionaries (Context.set_compress_dictionaries)
+  * train_dictionary / Context.train_dictionary_device : a zstd dictionary made from samples on the device
 All decoding and compression runs in the HIP kernels; nothing here decodes or compresses on the CPU.
 """
 from __future__ import annotations
@@ -18,7 +19,7 @@ import weakref
 import numpy as np
 
 from . import status
-from ._lib import (COMPRESS_CHECKSUM, COMPRESS_FSE_TABLES, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, COMPRESS_SPLIT, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
+from ._lib import (COMPRESS_CHECKSUM, COMPRESS_FSE_TABLES, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, COMPRESS_SPLIT, TRAIN_MIN_CAPACITY, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
                    BlockHeader, FrameHeader, build, lib)
 
 DEBUG_CHAIN_CPP_STEP, DEBUG_NO_HUF1, DEBUG_WX_POISON, DEBUG_EXEC_FIRST, DEBUG_EXEC_LEAVE = 1, 2, 4, 8, 16     # cz_context_set_debug_flags
@@ -28,7 +29,7 @@ __all__ = ["Context", "FrameDecoder", "BlockDecodingStrategy", "decode_batch_hos
            "read_block_header", "graph_replay_available", "RESULT_DTYPE", "RESULT_FINISHED", "RESULT_HAS_CHECKSUM", "RESULT_CHECKSUM_COMPUTED",
            "RESULT_CHECKSUM_MATCH", "status", "CzError", "build", "lib", "compress_bound", "compress_batch_host", "compress",
            "COMPRESS_CHECKSUM", "COMPRESS_RESULT_DTYPE", "compress_batch_host_dict", "COMPRESS_NO_DICT", "COMPRESS_NO_DICT_ID",
-           "COMPRESS_SPLIT", "compress_split_segment", "COMPRESS_FSE_TABLES"]
+           "COMPRESS_SPLIT", "compress_split_segment", "COMPRESS_FSE_TABLES", "train_dictionary", "TRAIN_MIN_CAPACITY"]
 
 
 def _as_u8(b) -> np.ndarray:
@@ -337,6 +338,52 @@ class Context:
         if st:
             raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
         return res
+
+    def train_dictionary_device(self, base: int, off: int, length: int, n: int, d_dict: int, capacity: int, dict_id: int = 0,
+                                segment_len: int = 0) -> int:
+        """cz_dictionary_train_device: a zstd dictionary from n samples in HBM (raw device pointers: base, off[] and len[] as uint64)
+        into the capacity bytes at d_dict.  Returns the dictionary's length.  Synchronises."""
+        params = (C.c_uint32 * 8)(dict_id, segment_len)
+        got = C.c_size_t(0)
+        st = lib().cz_dictionary_train_device(self._h, base, off, length, n, d_dict, capacity, params, C.byref(got))
+        if st:
+            raise CzError(st, f"cz_dictionary_train_device (hip error {lib().cz_context_last_hip_error(self._h)})")
+        return int(got.value)
+
+    def train_dictionary_host(self, base, off, length, capacity: int, dict_id: int = 0, segment_len: int = 0, fill: int = 0):
+        """cz_dictionary_train_host: the same from host arrays.  Returns (the whole capacity-byte buffer, pre-set to `fill`; the
+        dictionary's length)."""
+        base = _as_u8(base)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        length = np.ascontiguousarray(length, dtype=np.uint64)
+        out = np.full(max(int(capacity), 1), fill, dtype=np.uint8)
+        params = (C.c_uint32 * 8)(dict_id, segment_len)
+        got = C.c_size_t(0)
+        st = lib().cz_dictionary_train_host(self._h, base.ctypes.data if base.size else None, base.size, off.ctypes.data, length.ctypes.data,
+                                            int(off.size), out.ctypes.data, capacity, params, C.byref(got))
+        if st:
+            raise CzError(st, f"cz_dictionary_train_host (hip error {lib().cz_context_last_hip_error(self._h)})")
+        return out, int(got.value)
+
+    def last_train_ms(self):
+        """cz_dictionary_train_last_ms: device milliseconds of the last training's steps (frequencies, epochs, statistics, tables)."""
+        ms = (C.c_float * 4)()
+        st = lib().cz_dictionary_train_last_ms(self._h, ms)
+        if st:
+            raise CzError(st, "cz_dictionary_train_last_ms")
+        return [float(x) for x in ms]
+
+
+def train_dictionary(samples, capacity: int, ctx: Context, dict_id: int = 0, segment_len: int = 0) -> bytes:
+    """A zstd dictionary of at most `capacity` bytes trained on the device from `samples` (a list of buffers): content chosen by
+    d-mer coverage, entropy tables from parsing the samples against it.  dict_id 0: derived from the content; segment_len 0: 128."""
+    lens = np.array([len(b) for b in samples], dtype=np.uint64)
+    off = np.zeros(len(samples), dtype=np.uint64)
+    if len(samples) > 1:
+        off[1:] = np.cumsum(lens[:-1])
+    base = np.frombuffer(b"".join(bytes(b) for b in samples) + b"\0" * 16, dtype=np.uint8)
+    out, n = ctx.train_dictionary_host(base, off, lens, capacity, dict_id=dict_id, segment_len=segment_len)
+    return out[:n].tobytes()
 
 
 def _compress_flags(checksum, split, fse_tables) -> int:

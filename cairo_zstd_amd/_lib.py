@@ -23,6 +23,7 @@ COMPRESS_RESULT_DTYPE = np.dtype([("status", "<i4"), ("blocks", "<u4"), ("bytes_
                                   ("checksum", "<u4"), ("flags", "<u4")])
 assert COMPRESS_RESULT_DTYPE.itemsize == 32
 COMPRESS_CHECKSUM = 1
+TRAIN_MIN_CAPACITY = 1024               # cz_dictionary_train_*: the smallest dict_cap
 COMPRESS_NO_DICT_ID = 2                 # omit the Dictionary_ID field (cz_compress_batch_dict_*)
 COMPRESS_SPLIT = 4                      # cut inputs longer than compress_split_segment() into segments compressed side by side
 COMPRESS_FSE_TABLES = 16                # per-block FSE tables for the sequences where they make the block smaller
@@ -163,6 +164,12 @@ def lib() -> C.CDLL:
     L.cz_compress_batch_dict_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, C.c_uint32, vp, vp]
     L.cz_compress_batch_dict_host.restype = C.c_int
     L.cz_compress_batch_dict_host.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, C.c_uint32, vp, vp]
+    L.cz_dictionary_train_device.restype = C.c_int
+    L.cz_dictionary_train_device.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, C.POINTER(sz)]
+    L.cz_dictionary_train_host.restype = C.c_int
+    L.cz_dictionary_train_host.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, vp, C.POINTER(sz)]
+    L.cz_dictionary_train_last_ms.restype = C.c_int
+    L.cz_dictionary_train_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.cz_partition_balanced.restype = C.c_int
     L.cz_partition_balanced.argtypes = [vp, sz, sz, vp]
     L.cz_decode_batch_multi.restype = C.c_int

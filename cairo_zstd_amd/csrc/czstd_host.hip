@@ -34,6 +34,7 @@
 #include "czstd_enc.hip"     /* cz_compress_frames_kernel */
 #include "czstd_encsplit.hip" /* cz_compress_plan_kernel, cz_compress_segments_kernel (CZ_COMPRESS_SPLIT) */
 #include "czstd_encfse.hip"   /* cz_compress_frames_fse_kernel, cz_compress_segments_fse_kernel (CZ_COMPRESS_FSE_TABLES) */
+#include "czstd_train.hip"    /* cz_train_*_kernel (cz_dictionary_train_*) */
 #ifdef CZ_EXP_PAD   /* diagnostic: shifts the code objects behind it by CZ_EXP_PAD x 256 bytes (does the layout of the kernels in the code object matter?) */
 extern "C" __global__ void cz_pad_kernel(uint32_t* p) {
 #pragma unroll
@@ -110,6 +111,7 @@ struct cz_context {
     uint8_t* encf_scratch = nullptr; int encf_slots = 0; int encf_grid = 0;
     uint8_t* encfs_scratch = nullptr; int encfs_slots = 0; int encfs_grid = 0;
     cze_dict_entry* enc_dicts = nullptr; uint32_t enc_dict_count = 0; int enc_dgrid = 0;   /* cz_context_set_compress_dictionaries */
+    float train_ms[4] = {0.f, 0.f, 0.f, 0.f};                           /* cz_dictionary_train_last_ms */
     /* staging for cz_decode_batch_host */
     void* d_stage = nullptr; size_t d_stage_bytes = 0;
     void* h_pin = nullptr; size_t h_pin_bytes = 0;                      /* pinned host staging of cz_decode_batch_multi's share */
@@ -1196,6 +1198,110 @@ CZ_EXPORT int cz_compress_batch_dict_host(cz_context* c, const void* in_base, si
         [&](const void* i, const uint64_t* io, const uint64_t* il, void* o, const uint64_t* oo, const uint64_t* oc, const uint32_t* di, cz_compress_result* r) {
             return cz_compress_batch_dict_device(c, i, io, il, n, o, oo, oc, flags, di, r);
         });
+}
+
+/* ------------------------------------------------------------------ dictionary training (czstd_train.hip) */
+CZ_EXPORT int cz_dictionary_train_device(cz_context* c, const void* d_base, const uint64_t* d_off, const uint64_t* d_len, size_t n,
+                                         void* d_dict, size_t dict_cap, const cz_train_params* params, size_t* dict_len) try {
+    if (!c || !d_base || !d_off || !d_len || !d_dict || !dict_len) return CZ_E_INVALID_ARG;
+    int st = cz_train_check_params(n, dict_cap, params); if (st) return st;
+    cz_train_params pr; memset(&pr, 0, sizeof pr);
+    if (params) pr = *params;
+    CZ_HIP(c, hipSetDevice(c->device));
+    /* the lengths come to the host once: the checks, and the position of every sample in the sequence of all of them */
+    std::vector<uint64_t> len(n);
+    std::vector<uint32_t> cum(n + 1);
+    CZ_HIP(c, hipMemcpyAsync(len.data(), d_len, n * 8, hipMemcpyDeviceToHost, c->stream));
+    CZ_HIP(c, hipStreamSynchronize(c->stream));
+    st = cz_train_check_lengths(len.data(), n, cum.data()); if (st) return st;
+    const uint64_t total = cum[n];
+    const cz_train_plan plan = cz_train_make_plan(dict_cap, pr.segment_len, (uint32_t)total);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_freq = 0, o_htab = o_freq + (sizeof(uint32_t) << CZT_FREQ_LOG), o_state = o_htab + (sizeof(uint32_t) << CZE_HASH_LOG);
+    const size_t o_cum = o_state + up(sizeof(cz_train_state)), o_content = o_cum + up((n + 1) * 4), bytes = o_content + up(plan.content_cap);
+    uint8_t* d = nullptr;
+    CZ_HIP(c, hipMalloc((void**)&d, bytes));
+    struct Free { uint8_t* p; ~Free() { (void)hipFree(p); } } guard{d};
+    cz_train_args a; memset(&a, 0, sizeof a);
+    a.base = (const uint8_t*)d_base; a.off = d_off; a.len = d_len; a.cum = (const uint32_t*)(d + o_cum); a.n = (uint32_t)n; a.total = (uint32_t)total;
+    a.seg_len = plan.seg_len; a.segments = plan.segments; a.content_cap = plan.content_cap; a.dict_id = pr.dict_id;
+    a.freq = (uint32_t*)(d + o_freq); a.htab = (uint32_t*)(d + o_htab); a.content = d + o_content; a.st = (cz_train_state*)(d + o_state);
+    a.dict = (uint8_t*)d_dict;
+    cz_train_state st0; memset(&st0, 0, sizeof st0); st0.cursor = plan.content_cap;
+    CZ_HIP(c, hipMemsetAsync(d, 0, o_state, c->stream));
+    CZ_HIP(c, hipMemcpyAsync(a.st, &st0, sizeof st0, hipMemcpyHostToDevice, c->stream));
+    CZ_HIP(c, hipMemcpyAsync(d + o_cum, cum.data(), (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct Events { hipEvent_t* e; ~Events() { for (int i = 0; i < 5; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evguard{ev};
+    for (int i = 0; i < 5; i++) CZ_HIP(c, hipEventCreate(&ev[i]));
+    const unsigned wide = (unsigned)std::min<uint64_t>((total + CZT_THREADS - 1) / CZT_THREADS, (uint64_t)c->num_cu * 8u);
+    CZ_HIP(c, hipEventRecord(ev[0], c->stream));
+    if (total <= plan.content_cap) {
+        hipLaunchKernelGGL(cz_train_concat_kernel, dim3((unsigned)std::min<size_t>(n, 1024)), dim3(CZT_THREADS), 0, c->stream, a);
+        CZ_HIP(c, hipGetLastError());
+        CZ_HIP(c, hipEventRecord(ev[1], c->stream));
+    } else {
+        hipLaunchKernelGGL(cz_train_freq_kernel, dim3(wide), dim3(CZT_THREADS), 0, c->stream, a);
+        CZ_HIP(c, hipGetLastError());
+        CZ_HIP(c, hipEventRecord(ev[1], c->stream));
+        /* the rounds, a pass over all ranges at a time; between passes the host looks whether the content is full */
+        const unsigned tiles = (plan.max_range + CZT_TILE - 1) / CZT_TILE;
+        for (uint32_t r = 0; r < plan.rounds;) {
+            for (uint32_t k = 0; k < plan.segments; k++, r++) {
+                hipLaunchKernelGGL(cz_train_score_kernel, dim3(tiles), dim3(CZT_THREADS), 0, c->stream, a, r);
+                hipLaunchKernelGGL(cz_train_commit_kernel, dim3(1), dim3(CZT_THREADS), 0, c->stream, a);
+            }
+            CZ_HIP(c, hipGetLastError());
+            cz_train_state now;
+            CZ_HIP(c, hipMemcpyAsync(&now, a.st, 32, hipMemcpyDeviceToHost, c->stream));
+            CZ_HIP(c, hipStreamSynchronize(c->stream));
+            if (now.cursor < plan.seg_len) break;
+        }
+    }
+    CZ_HIP(c, hipEventRecord(ev[2], c->stream));
+    hipLaunchKernelGGL(cz_train_image_kernel, dim3(plan.content_cap / (16 * CZT_THREADS) + 1), dim3(CZT_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(cz_train_stats_kernel, dim3((unsigned)std::min<size_t>(n, (size_t)c->num_cu * 2)), dim3(CZT_THREADS), 0, c->stream, a);
+    CZ_HIP(c, hipGetLastError());
+    CZ_HIP(c, hipEventRecord(ev[3], c->stream));
+    hipLaunchKernelGGL(cz_train_finish_kernel, dim3(1), dim3(CZT_THREADS), 0, c->stream, a);
+    CZ_HIP(c, hipGetLastError());
+    CZ_HIP(c, hipEventRecord(ev[4], c->stream));
+    cz_train_state fin;
+    CZ_HIP(c, hipMemcpyAsync(&fin, a.st, 32, hipMemcpyDeviceToHost, c->stream));
+    CZ_HIP(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 4; i++) { float ms = 0.f; c->train_ms[i] = hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess ? ms : 0.f; }
+    if (fin.status) return (int)fin.status;
+    *dict_len = fin.dict_len;
+    return CZ_OK;
+} catch (const std::bad_alloc&) { return CZ_E_OUT_OF_MEMORY; }
+
+CZ_EXPORT int cz_dictionary_train_host(cz_context* c, const void* base, size_t bytes, const uint64_t* off, const uint64_t* len, size_t n,
+                                       void* dict, size_t dict_cap, const cz_train_params* params, size_t* dict_len) {
+    if (!c || !base || !off || !len || !dict || !dict_len) return CZ_E_INVALID_ARG;
+    int st = cz_train_check_params(n, dict_cap, params); if (st) return st;
+    for (size_t i = 0; i < n; i++) if (off[i] > bytes || len[i] > bytes - off[i]) return CZ_E_INVALID_ARG;
+    CZ_HIP(c, hipSetDevice(c->device));
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_in = 0, o_desc = o_in + up(bytes + 16), o_dict = o_desc + up(2 * n * 8), total = o_dict + up(dict_cap);
+    st = cz_stage_reserve(c, total); if (st) return st;
+    uint8_t* d = (uint8_t*)c->d_stage;
+    uint64_t* d_desc = (uint64_t*)(d + o_desc);
+    CZ_HIP(c, hipMemcpyAsync(d + o_in, base, bytes, hipMemcpyHostToDevice, c->stream));
+    CZ_HIP(c, hipMemcpyAsync(d_desc, off, n * 8, hipMemcpyHostToDevice, c->stream));
+    CZ_HIP(c, hipMemcpyAsync(d_desc + n, len, n * 8, hipMemcpyHostToDevice, c->stream));
+    size_t got = 0;
+    st = cz_dictionary_train_device(c, d + o_in, d_desc, d_desc + n, n, d + o_dict, dict_cap, params, &got);
+    if (st) return st;
+    CZ_HIP(c, hipMemcpyAsync(dict, d + o_dict, got, hipMemcpyDeviceToHost, c->stream));
+    CZ_HIP(c, hipStreamSynchronize(c->stream));
+    *dict_len = got;
+    return CZ_OK;
+}
+/* the time the last cz_dictionary_train_* spent in its four steps (frequencies, epochs, statistics, tables), in ms */
+CZ_EXPORT int cz_dictionary_train_last_ms(cz_context* c, float ms[4]) {
+    if (!c || !ms) return CZ_E_INVALID_ARG;
+    for (int i = 0; i < 4; i++) ms[i] = c->train_ms[i];
+    return CZ_OK;
 }
 
 /* ------------------------------------------------------------------ several devices */

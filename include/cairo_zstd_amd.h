@@ -521,6 +521,35 @@ int cz_compress_batch_dict_host(cz_context* ctx, const void* in_base, size_t in_
                                 void* out_base, size_t out_bytes, const uint64_t* out_off, const uint64_t* out_cap, uint32_t flags,
                                 const uint32_t* dict_index, cz_compress_result* results);
 
+/* ---- dictionary training ----
+ * Makes a standard zstd dictionary from samples on the device: magic 0xEC30A437, Dictionary_ID, the Huffman description of the
+ * literals, the FSE descriptions of OF, ML and LL, the repeat offsets 1, 4, 8, then the content.  The content is chosen as
+ * fastCover chooses it (8-byte d-mers counted in 2^20 hashed counters; round after round the window of segment_len bytes with the
+ * highest sum of counters, each d-mer once, from one of content_capacity / segment_len equal ranges of the samples; windows chosen
+ * earlier lie nearer the end).  The tables come from parsing every sample against that content as cz_compress_batch_dict_* would;
+ * every literal value and every LL (0..35), ML (0..52) and OF (0..20) code has a state, so libzstd takes the tables as valid and
+ * this library's compressor writes Repeat_Mode with them.  When all samples together fit the content it is all of them, in order.
+ * The bytes depend on the samples in their order, dict_cap and the parameters only.  dict_cap - 320 bytes are the content's room
+ * (at most 1 GiB); *dict_len <= dict_cap, and no byte past *dict_len is written.
+ * CZ_E_INVALID_ARG (nothing written): dict_cap < CZ_TRAIN_MIN_CAPACITY, n == 0, a non-zero reserved word, a segment_len outside
+ * its range, 2 GiB of samples or more, no sample of 8 bytes or more, a NULL pointer other than params.
+ * Synchronises the context's stream (training is set-up, like cz_context_measure_batch). */
+typedef struct cz_train_params {
+    uint32_t dict_id;      /* 0: 32768 + XXH64(content) % (2^31 - 32768), as ZDICT derives it */
+    uint32_t segment_len;  /* 0: the default, CZ_TRAIN_SEGMENT; else 16 .. 4096 */
+    uint32_t reserved[6];  /* must be 0 */
+} cz_train_params;
+#define CZ_TRAIN_SEGMENT 128
+#define CZ_TRAIN_MIN_CAPACITY 1024
+/* Samples: DEVICE pointers, laid out like a batch (base + off[] + len[]).  d_dict: DEVICE, dict_cap bytes.  params NULL: defaults. */
+int cz_dictionary_train_device(cz_context* ctx, const void* d_base, const uint64_t* d_off, const uint64_t* d_len, size_t n,
+                               void* d_dict, size_t dict_cap, const cz_train_params* params, size_t* dict_len);
+/* Same with HOST buffers (bytes: the size of base; a sample outside it is CZ_E_INVALID_ARG). */
+int cz_dictionary_train_host(cz_context* ctx, const void* base, size_t bytes, const uint64_t* off, const uint64_t* len, size_t n,
+                             void* dict, size_t dict_cap, const cz_train_params* params, size_t* dict_len);
+/* Milliseconds on the device of the last training's four steps: frequencies, epochs, statistics, tables and header. */
+int cz_dictionary_train_last_ms(cz_context* ctx, float ms[4]);
+
 #ifdef __cplusplus
 }
 #endif
