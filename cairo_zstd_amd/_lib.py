@@ -27,6 +27,7 @@ TRAIN_MIN_CAPACITY = 1024               # cz_dictionary_train_*: the smallest di
 COMPRESS_NO_DICT_ID = 2                 # omit the Dictionary_ID field (cz_compress_batch_dict_*)
 COMPRESS_SPLIT = 4                      # cut inputs longer than compress_split_segment() into segments compressed side by side
 COMPRESS_FSE_TABLES = 16                # per-block FSE tables for the sequences where they make the block smaller
+COMPRESS_FAST = 32                      # the fast level: 32 KiB blocks that stand alone, one wave each (not with SPLIT or FSE_TABLES)
 COMPRESS_NO_DICT = 0xFFFFFFFF           # dict_index entry: no dictionary for this buffer
 
 

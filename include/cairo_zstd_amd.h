@@ -470,6 +470,22 @@ uint64_t cz_compress_split_segment(void);   /* the segment size S in bytes */
  * Predefined ones, and mixing a dictionary's tables with the frame's own is left for later.
  */
 #define CZ_COMPRESS_FSE_TABLES 16u
+/*
+ * CZ_COMPRESS_FAST (cz_compress_batch_device / _host only, alone or with CZ_COMPRESS_CHECKSUM): the fast level.
+ * The frame header, the optional checksum and the limits are as without the flag; an empty input comes out byte for byte the same.
+ * The input is cut into groups of 128 KiB and every group into sub-blocks of 32 KiB (the last of each may be shorter); every
+ * sub-block becomes one block, Raw, RLE or Compressed, whichever is smallest (below 16 bytes: Raw or RLE), with the literal rules
+ * above and the Predefined sequence tables, compressed by one wave on a hash table of its own.  Every block can be decoded without
+ * any other block of the frame: no match reaches in front of its sub-block, Treeless literals and Repeat_Mode are never written, and
+ * Offset_Value 1 only refers to an offset that an earlier sequence of the same block wrote explicitly.  A group whose blocks, headers
+ * included, exceed 3 + its size is written as ONE Raw block of the group's size, so cz_compress_bound still holds although a frame may
+ * hold four times as many blocks.  `blocks` counts the blocks written; CZ_E_OUTPUT_TOO_SMALL ends the frame at a group boundary
+ * (bytes_written / bytes_read / blocks cover the whole groups placed, nothing past bytes_written is touched).  The bytes depend on
+ * the input and the flags alone.  The result flags carry the bit whenever it was requested.  The value is 32: 8 stays an unknown bit.
+ * CZ_E_INVALID_ARG together with CZ_COMPRESS_SPLIT or CZ_COMPRESS_FSE_TABLES and in cz_compress_batch_dict_*: these combinations
+ * are left for later.
+ */
+#define CZ_COMPRESS_FAST 32u
 /* One per buffer, written by the device. */
 typedef struct cz_compress_result {
     int32_t  status;            /* CZ_OK | CZ_E_OUTPUT_TOO_SMALL | CZ_E_INVALID_ARG (an input of 4 GiB - 1 MiB or more) | CZ_E_WAIT_EXPIRED */
@@ -482,7 +498,8 @@ typedef struct cz_compress_result {
 /* Compresses in_base[in_off[i] .. +in_len[i]) into out_base[out_off[i] .. +out_cap[i]) for every i < n.  DEVICE pointers
  * (results too); asynchronous on the context stream; no alignment required.  A frame that fails leaves its neighbours and
  * every byte of its own region past bytes_written untouched.  out_cap[i] = cz_compress_bound(in_len[i]) always suffices.
- * flags: CZ_COMPRESS_CHECKSUM, CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES; any other bit is CZ_E_INVALID_ARG. */
+ * flags: CZ_COMPRESS_CHECKSUM, CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES, CZ_COMPRESS_FAST (not with the two before it); any other
+ * bit is CZ_E_INVALID_ARG. */
 int cz_compress_batch_device(cz_context* ctx, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                              void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                              cz_compress_result* d_results);
@@ -511,8 +528,8 @@ int cz_context_set_compress_dictionaries(cz_context* ctx, const cz_dictionary* c
  * CZ_COMPRESS_NO_DICT (the frame then comes out byte for byte as from cz_compress_batch_device).  Any other index >= k fails that
  * frame alone with CZ_E_INVALID_ARG (nothing written), as does a dictionary content plus input of 4 GiB - 1 MiB or more.
  * d_dict_index (DEVICE, n entries) may be NULL when exactly one dictionary is set: every frame uses it.  flags: CZ_COMPRESS_CHECKSUM,
- * CZ_COMPRESS_NO_DICT_ID (CZ_COMPRESS_SPLIT and CZ_COMPRESS_FSE_TABLES are CZ_E_INVALID_ARG here: split frames take no dictionary,
- * and dictionary frames no tables of their own). */
+ * CZ_COMPRESS_NO_DICT_ID (CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES and CZ_COMPRESS_FAST are CZ_E_INVALID_ARG here: split frames take
+ * no dictionary, dictionary frames no tables of their own, and the fast level has no dictionary kernel yet). */
 int cz_compress_batch_dict_device(cz_context* ctx, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                                   void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                                   const uint32_t* d_dict_index, cz_compress_result* d_results);
