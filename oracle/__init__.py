@@ -96,6 +96,8 @@ def lib() -> C.CDLL:
         L.czo_set_d1_reference_nibbles.argtypes = [C.c_int]
         L.czo_dump_sequences.restype = C.c_int
         L.czo_dump_sequences.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.czo_dump_sequences_with_dict.restype = C.c_int
+        L.czo_dump_sequences_with_dict.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.czo_libzstd_batch.restype = C.c_long
         L.czo_libzstd_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         _lib = L
@@ -143,13 +145,16 @@ def huf_code_lengths(desc):
     return st, lengths, used.value
 
 
-def dump_sequences(src, cap: int, max_sequences: int = 1 << 20):
+def dump_sequences(src, cap: int, max_sequences: int = 1 << 20, dictionary: "Dictionary | None" = None):
     """Every sequence of a frame as the oracle decodes it, in order across blocks: (status, [(literal length, match length,
-    Offset_Value)])."""
+    Offset_Value)]).  dictionary: the Dictionary the frame was written against."""
     a = _buf(src)
     out = np.zeros(3 * max_sequences, dtype=np.uint32)
     n = C.c_size_t()
-    st = lib().czo_dump_sequences(a.ctypes.data, a.size, cap, out.ctypes.data, max_sequences, C.byref(n))
+    if dictionary is None:
+        st = lib().czo_dump_sequences(a.ctypes.data, a.size, cap, out.ctypes.data, max_sequences, C.byref(n))
+    else:
+        st = lib().czo_dump_sequences_with_dict(a.ctypes.data, a.size, dictionary._h, out.ctypes.data, max_sequences, C.byref(n))
     k = min(n.value, max_sequences)
     return st, [tuple(int(v) for v in out[3 * i:3 * i + 3]) for i in range(k)]
 

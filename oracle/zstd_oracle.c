@@ -1285,6 +1285,22 @@ CZO_API int czo_dump_sequences(const uint8_t* src, size_t len, size_t cap, uint3
     *count = g_dump_n;
     return e;
 }
+/* the same for a frame written against a dictionary: new -> init_from_dict -> decode_blocks(All), as czo_fd_init_from_dict's callers do */
+CZO_API int czo_dump_sequences_with_dict(const uint8_t* src, size_t len, const czo_dictionary* dict, uint32_t* out, size_t out_cap, size_t* count) {
+    *count = 0;
+    czo_frame_decoder* d = czo_fd_create(); if (!d) return CZ_E_INVALID_ARG;
+    size_t hl = 0, used = 0; int fin = 0; uint64_t detail[2] = {0, 0};
+    g_dump_out = out; g_dump_cap = out_cap; g_dump_n = 0;
+    int e = czo_fd_new(d, src, len, &hl, detail);
+    if (!e) e = scratch_init_from_dict(&d->sc, dict);
+    g_seq_hook = dump_hook;
+    if (!e) e = czo_fd_decode_blocks(d, src + hl, len - hl, 0, 0, &used, &fin);
+    g_seq_hook = NULL;
+    if (!e && !czo_fd_is_finished(d)) e = CZ_E_NOT_FINISHED;
+    czo_fd_destroy(d);
+    *count = g_dump_n;
+    return e;
+}
 
 CZO_API int czo_abi_version(void) { return 1; }
 

@@ -194,16 +194,26 @@ def weight_norm(lengths):
 
 
 # -------------------------------------------------------------------------------------------------------------- frame analysis
-def analyse(frame, data):
+def analyse(frame, data, dictionary=None):
     """parse_frame, plus per block: the sequences the oracle decodes (literal length, match length, Offset_Value, the actual
     offset), their LL / ML / OF codes, the block's literal bytes and histogram, and for Huffman literals the code lengths the oracle
-    reads from the tree description."""
+    reads from the tree description.  dictionary: the raw dictionary the frame was written against; the offset history then starts
+    from its three offsets, every offset must stay inside content + the data before the match, and the bytes each match copies are
+    checked against content + data."""
     import oracle
     fr = parse_frame(frame)
-    st, seqs = oracle.dump_sequences(frame, cap=len(data) + 64)
+    hist3, content = [1, 4, 8], b""
+    if dictionary is None:
+        st, seqs = oracle.dump_sequences(frame, cap=len(data) + 64)
+    else:
+        od = oracle.Dictionary(dictionary)
+        assert od.status == 0, od.status
+        st, seqs = oracle.dump_sequences(frame, cap=len(data) + 64, dictionary=od)
+        hist3 = [od.info["hist0"], od.info["hist1"], od.info["hist2"]]
+        content = bytes(dictionary)[od.info["content_off"]:]
     assert st == 0, st
     k, b0 = 0, 0
-    hist3 = [1, 4, 8]
+    D = len(content)
     for blk in fr["blocks"]:
         bsize = blk["size"]                                     # Raw and RLE blocks; a compressed block's from its sequences
         blk["seqs"] = []
@@ -225,7 +235,11 @@ def analyse(frame, data):
                         hist3 = [off, hist3[0], hist3[1]]
                 offs.append(off)
                 lits += data[pos:pos + ll]
-                pos += ll + ml
+                pos += ll
+                if dictionary is not None:
+                    assert 0 < off <= D + pos, (off, D, pos)
+                    _check_copy(content, data, pos, off, ml)
+                pos += ml
             nlit_tail = blk["lit"]["regen"] - len(lits)         # the literals after the last sequence
             lits += data[pos:pos + nlit_tail]
             pos += nlit_tail
@@ -249,6 +263,14 @@ def analyse(frame, data):
                 lit["lengths"], lit["desc_len"] = lengths, used
     assert k == len(seqs) and b0 == len(data)
     return fr
+
+
+def _check_copy(content, data, pos, off, ml):
+    """The ml bytes a match at data[pos] with this offset copies, read from content + data, are data[pos:pos + ml]."""
+    D, src = len(content), len(content) + pos - off                     # virtual position of the first byte copied
+    n = min(ml, max(0, D - src))                                        # bytes that come from the content
+    assert content[src:src + n] == data[pos:pos + n], (pos, off, ml)
+    assert pos + ml <= len(data) and data[pos + n:pos + ml] == data[pos + n - off:pos + ml - off], (pos, off, ml)   # the rest from the data
 
 
 # ---------------------------------------------------------------------------------------------------------------- input builders

@@ -2,10 +2,11 @@
  * TEST INFRASTRUCTURE ONLY — runs the dictionary compressor (the unmodified czstd_enc.hip and czstd_kernels.hip) on the CPU through
  * tests/emu/hip/hip_runtime.h, under ASan+UBSan: each dictionary parsed by cz_dict_setup_kernel, prepared by cz_enc_dict_prep_kernel
  * (a grid of two), then cz_compress_frames_dict_kernel (a grid of two), one workgroup at a time.
- * usage: emu_encode_dict <batch.bin> <result.bin>
+ * usage: emu_encode_dict <batch.bin> <result.bin> [<tables.bin>]
  *   batch.bin : u64 n, u32 flags, u32 k, k x { u64 len, dictionary bytes }, u32 has_index, then n x { u64 in_len, u64 out_cap,
  *               u32 dict_index, in bytes }
  *   result.bin: n x { cz_compress_result, the whole output region (out_cap bytes; 0xEE where nothing was written) }
+ *   tables.bin: k x the prepared hash table (CzeDict::htab, 2^14 u32) of each dictionary, as cz_enc_dict_prep_kernel left it
  * Inputs sit one byte past the start of an exact-size heap block (unaligned), outputs in another exact-size block, each dictionary
  * in an exact-size block of its own.
  */
@@ -101,6 +102,11 @@ int main(int argc, char** argv) {
         run_lanes(proto, CZE_THREADS, 2);
         table[j].img = img; table[j].content = raw + res[1]; table[j].content_len = dl - res[1]; table[j].id = (uint32_t)res[2];
         for (int q = 0; q < 3; q++) table[j].rep[q] = st->hist[q];
+    }
+    if (argc > 3) {
+        FILE* tf = fopen(argv[3], "wb"); if (!tf) return 2;
+        for (uint32_t j = 0; j < k; j++) fwrite(table[j].img->htab, 4, 1u << CZE_HASH_LOG, tf);
+        fclose(tf);
     }
     if (fread(&has_index, 4, 1, f) != 1) return 2;
     std::vector<uint64_t> in_off(n), in_len(n), out_off(n), out_cap(n);

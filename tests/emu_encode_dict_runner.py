@@ -23,9 +23,10 @@ def build():
     return os.path.join(EMU_DIR, "emu_encode_dict")
 
 
-def run(buffers, dicts, index=None, caps=None, flags=0, timeout=1800):
+def run(buffers, dicts, index=None, caps=None, flags=0, timeout=1800, tables=False):
     """[(result record, whole output region — 0xEE where nothing was written)] per buffer.  dicts: raw dictionaries (bytes);
-    index: one entry per buffer (NO_DICT: none) or None (the kernel is given no index: every frame uses dicts[0])."""
+    index: one entry per buffer (NO_DICT: none) or None (the kernel is given no index: every frame uses dicts[0]).
+    tables=True: (that list, [the prepared hash table of each dictionary, 2^14 uint32])."""
     exe = build()
     caps = [compress_bound(len(b)) for b in buffers] if caps is None else list(caps)
     with tempfile.TemporaryDirectory() as td:
@@ -40,14 +41,16 @@ def run(buffers, dicts, index=None, caps=None, flags=0, timeout=1800):
                 f.write(struct.pack("<QQI", len(b), cap, 0 if index is None else index[i]))
                 f.write(bytes(b))
         env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-        p = subprocess.run([exe, inp, outp], capture_output=True, timeout=timeout, env=env)
+        tabp = os.path.join(td, "tables.bin")
+        p = subprocess.run([exe, inp, outp] + ([tabp] if tables else []), capture_output=True, timeout=timeout, env=env)
         if p.returncode != 0:
             raise RuntimeError(f"emu_encode_dict failed rc={p.returncode}\n{p.stderr.decode()[-4000:]}")
         raw = open(outp, "rb").read()
+        tabs = np.fromfile(tabp, dtype=np.uint32).reshape(len(dicts), 1 << 14) if tables else None
     out, pos = [], 0
     for cap in caps:
         r = np.frombuffer(raw, dtype=COMPRESS_RESULT_DTYPE, count=1, offset=pos)[0]
         pos += COMPRESS_RESULT_DTYPE.itemsize
         out.append((r, raw[pos:pos + cap]))
         pos += cap
-    return out
+    return (out, list(tabs)) if tables else out

@@ -41,11 +41,12 @@ def dicts(cz, ctx):
     return ds
 
 
-def device_compress(cz, ctx, bufs, idx, caps=None, checksum=False, dict_id=True):
-    """Through cz_compress_batch_dict_device with torch buffers: inputs at odd offsets, output regions poisoned."""
+def device_compress(cz, ctx, bufs, idx, caps=None, checksum=False, dict_id=True, in_shift=0):
+    """Through cz_compress_batch_dict_device with torch buffers: inputs at odd offsets (moved by in_shift), output regions poisoned;
+    the gaps between the regions must stay poisoned."""
     import torch
     lens = [len(b) for b in bufs]
-    in_off = np.cumsum([3] + [l + 1 for l in lens[:-1]]).astype(np.uint64)
+    in_off = np.cumsum([3 + in_shift] + [l + 1 for l in lens[:-1]]).astype(np.uint64)
     host_in = np.zeros(int(in_off[-1]) + lens[-1] + 16, dtype=np.uint8)
     for o, b in zip(in_off, bufs):
         host_in[int(o):int(o) + len(b)] = np.frombuffer(b, dtype=np.uint8)
@@ -66,6 +67,9 @@ def device_compress(cz, ctx, bufs, idx, caps=None, checksum=False, dict_id=True)
     out = d_out.cpu().numpy()
     res = d_res.cpu().numpy().view(cz.COMPRESS_RESULT_DTYPE)
     assert set(out[:int(out_off[0])].tolist()) == {POISON}
+    ends = [int(o) + c for o, c in zip(out_off, caps)]
+    for i, (a, b) in enumerate(zip(ends, [int(o) for o in out_off[1:]] + [total])):
+        assert (out[a:b] == POISON).all(), f"the gap behind region {i} was written"
     return [(res[i], out[int(out_off[i]):int(out_off[i]) + caps[i]].tobytes()) for i in range(len(bufs))]
 
 
