@@ -7,8 +7,9 @@ Python here is a thin mirror over the C ABI (include/cairo_zstd_amd.h, libcairo_
   * read_frame_header / read_block_header : stateless parsers
   * compress / compress_batch_host / Context.compress_batch_device : batched compression on the device (split=True: a large
     buffer on many workgroups, still one frame; fse_tables=True: per-block FSE tables for the sequences; fast=True: the fast
-    level, 32 KiB blocks that stand alone, one wave each)
-  * compress_batch_host_dict / Context.compress_batch_dict_device : the same with dictionaries (Context.set_compress_dictionaries)
+    level, 32 KiB blocks that stand alone, one wave each; records=True: the records level, one wave per buffer of at most 32 KiB)
+  * compress_batch_host_dict / Context.compress_batch_dict_device : the same with dictionaries (Context.set_compress_dictionaries;
+    records=True: the records level with dictionaries)
   * train_dictionary / Context.train_dictionary_device : a zstd dictionary made from samples on the device
 All decoding and compression runs in the HIP kernels; nothing here decodes or compresses on the CPU.
 """
@@ -20,7 +21,7 @@ import weakref
 import numpy as np
 
 from . import status
-from ._lib import (COMPRESS_CHECKSUM, COMPRESS_FAST, COMPRESS_FSE_TABLES, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, COMPRESS_SPLIT, TRAIN_MIN_CAPACITY, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
+from ._lib import (COMPRESS_CHECKSUM, COMPRESS_FAST, COMPRESS_RECORDS, COMPRESS_FSE_TABLES, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, COMPRESS_SPLIT, TRAIN_MIN_CAPACITY, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
                    BlockHeader, FrameHeader, build, lib)
 
 DEBUG_CHAIN_CPP_STEP, DEBUG_NO_HUF1, DEBUG_WX_POISON, DEBUG_EXEC_FIRST, DEBUG_EXEC_LEAVE = 1, 2, 4, 8, 16     # cz_context_set_debug_flags
@@ -30,7 +31,7 @@ __all__ = ["Context", "FrameDecoder", "BlockDecodingStrategy", "decode_batch_hos
            "read_block_header", "graph_replay_available", "RESULT_DTYPE", "RESULT_FINISHED", "RESULT_HAS_CHECKSUM", "RESULT_CHECKSUM_COMPUTED",
            "RESULT_CHECKSUM_MATCH", "status", "CzError", "build", "lib", "compress_bound", "compress_batch_host", "compress",
            "COMPRESS_CHECKSUM", "COMPRESS_RESULT_DTYPE", "compress_batch_host_dict", "COMPRESS_NO_DICT", "COMPRESS_NO_DICT_ID",
-           "COMPRESS_SPLIT", "compress_split_segment", "COMPRESS_FSE_TABLES", "COMPRESS_FAST", "train_dictionary", "TRAIN_MIN_CAPACITY"]
+           "COMPRESS_SPLIT", "compress_split_segment", "COMPRESS_FSE_TABLES", "COMPRESS_FAST", "COMPRESS_RECORDS", "compress_record_max", "train_dictionary", "TRAIN_MIN_CAPACITY"]
 
 
 def _as_u8(b) -> np.ndarray:
@@ -281,19 +282,21 @@ class Context:
 
     def compress_batch_device(self, in_base: int, in_off: int, in_len: int, n: int, out_base: int, out_off: int,
                               out_cap: int, results: int, checksum: bool = False, split: bool = False, fse_tables: bool = False,
-                              fast: bool = False):
+                              fast: bool = False, records: bool = False):
         """cz_compress_batch_device.  All arguments are raw DEVICE pointers (tensor.data_ptr()); `results` holds n
         COMPRESS_RESULT_DTYPE records.  Asynchronous on the context's stream, like decode_batch_device.  split=True
         (COMPRESS_SPLIT): inputs longer than compress_split_segment() are compressed by several workgroups, still one frame each.
         fse_tables=True (COMPRESS_FSE_TABLES): each block's sequences take tables of its own where they make it smaller.
-        fast=True (COMPRESS_FAST): the fast level, 32 KiB blocks that stand alone; not with split or fse_tables."""
+        fast=True (COMPRESS_FAST): the fast level, 32 KiB blocks that stand alone; not with split or fse_tables.
+        records=True (COMPRESS_RECORDS): the records level, one wave per input of at most compress_record_max() bytes; not with
+        split, fse_tables or fast."""
         st = lib().cz_compress_batch_device(self._h, in_base, in_off, in_len, n, out_base, out_off, out_cap,
-                                            _compress_flags(checksum, split, fse_tables, fast), results)
+                                            _compress_flags(checksum, split, fse_tables, fast, records), results)
         if st:
             raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
 
     def compress_batch_host(self, in_base, in_off, in_len, out_off, out_cap, out: np.ndarray, checksum: bool = False,
-                            split: bool = False, fse_tables: bool = False, fast: bool = False):
+                            split: bool = False, fse_tables: bool = False, fast: bool = False, records: bool = False):
         """cz_compress_batch_host: host buffers in, `out` (uint8, written in place) out.  Returns the result records."""
         in_base = _as_u8(in_base)
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
@@ -305,26 +308,27 @@ class Context:
         res = np.zeros(n, dtype=COMPRESS_RESULT_DTYPE)
         st = lib().cz_compress_batch_host(self._h, in_base.ctypes.data if in_base.size else None, in_base.size, in_off.ctypes.data,
                                           in_len.ctypes.data, n, out.ctypes.data, out.size, out_off.ctypes.data, out_cap.ctypes.data,
-                                          _compress_flags(checksum, split, fse_tables, fast), res.ctypes.data)
+                                          _compress_flags(checksum, split, fse_tables, fast, records), res.ctypes.data)
         if st:
             raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
         return res
 
     def compress_batch_dict_device(self, in_base: int, in_off: int, in_len: int, n: int, out_base: int, out_off: int,
-                                   out_cap: int, dict_index: int, results: int, checksum: bool = False, dict_id: bool = True):
+                                   out_cap: int, dict_index: int, results: int, checksum: bool = False, dict_id: bool = True,
+                                   records: bool = False):
         """cz_compress_batch_dict_device: as compress_batch_device, frame i with dictionary dict_index[i] of
         set_compress_dictionaries (COMPRESS_NO_DICT: none).  dict_index is a DEVICE pointer to n uint32 (0: every frame uses the
-        one dictionary set).  dict_id=False omits the Dictionary_ID field."""
-        flags = (COMPRESS_CHECKSUM if checksum else 0) | (0 if dict_id else COMPRESS_NO_DICT_ID)
+        one dictionary set).  dict_id=False omits the Dictionary_ID field.  records=True (COMPRESS_RECORDS): the records level."""
+        flags = (COMPRESS_CHECKSUM if checksum else 0) | (0 if dict_id else COMPRESS_NO_DICT_ID) | (COMPRESS_RECORDS if records else 0)
         st = lib().cz_compress_batch_dict_device(self._h, in_base, in_off, in_len, n, out_base, out_off, out_cap, flags,
                                                  dict_index or None, results)
         if st:
             raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
 
     def compress_batch_dict_host(self, in_base, in_off, in_len, out_off, out_cap, out: np.ndarray, dict_index,
-                                 checksum: bool = False, dict_id: bool = True):
+                                 checksum: bool = False, dict_id: bool = True, records: bool = False):
         """cz_compress_batch_dict_host: as compress_batch_host, with a dictionary index per buffer (None: every buffer uses the
-        one dictionary set).  Returns the result records."""
+        one dictionary set).  records=True (COMPRESS_RECORDS): the records level.  Returns the result records."""
         in_base = _as_u8(in_base)
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
         in_len = np.ascontiguousarray(in_len, dtype=np.uint64)
@@ -334,7 +338,7 @@ class Context:
         assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"]
         n = int(in_off.size)
         res = np.zeros(n, dtype=COMPRESS_RESULT_DTYPE)
-        flags = (COMPRESS_CHECKSUM if checksum else 0) | (0 if dict_id else COMPRESS_NO_DICT_ID)
+        flags = (COMPRESS_CHECKSUM if checksum else 0) | (0 if dict_id else COMPRESS_NO_DICT_ID) | (COMPRESS_RECORDS if records else 0)
         st = lib().cz_compress_batch_dict_host(self._h, in_base.ctypes.data if in_base.size else None, in_base.size, in_off.ctypes.data,
                                                in_len.ctypes.data, n, out.ctypes.data, out.size, out_off.ctypes.data, out_cap.ctypes.data,
                                                flags, None if idx is None else idx.ctypes.data, res.ctypes.data)
@@ -389,9 +393,11 @@ def train_dictionary(samples, capacity: int, ctx: Context, dict_id: int = 0, seg
     return out[:n].tobytes()
 
 
-def _compress_flags(checksum, split, fse_tables, fast=False) -> int:
+def _compress_flags(checksum, split, fse_tables, fast=False, records=False) -> int:
+    if records and (split or fse_tables or fast):
+        raise CzError(status.CZ_E_INVALID_ARG, "records goes with checksum alone: not with split, fse_tables or fast")
     return ((COMPRESS_CHECKSUM if checksum else 0) | (COMPRESS_SPLIT if split else 0) | (COMPRESS_FSE_TABLES if fse_tables else 0)
-            | (COMPRESS_FAST if fast else 0))
+            | (COMPRESS_FAST if fast else 0) | (COMPRESS_RECORDS if records else 0))
 
 
 def compress_bound(n: int) -> int:
@@ -404,12 +410,18 @@ def compress_split_segment() -> int:
     return int(lib().cz_compress_split_segment())
 
 
+def compress_record_max() -> int:
+    """cz_compress_record_max: the largest input COMPRESS_RECORDS takes, in bytes."""
+    return int(lib().cz_compress_record_max())
+
+
 def compress_batch_host(buffers, ctx: Context, checksum: bool = False, split: bool = False, fse_tables: bool = False,
-                        fast: bool = False):
+                        fast: bool = False, records: bool = False):
     """Compresses every buffer into one zstd frame, in one launch: list of (result record, frame bytes).  split=True: buffers
     longer than compress_split_segment() are compressed by several workgroups side by side (COMPRESS_SPLIT).  fse_tables=True:
     the sequences of a block take FSE tables made for that block where they make it smaller (COMPRESS_FSE_TABLES).  fast=True:
-    the fast level (COMPRESS_FAST), which the library refuses together with split or fse_tables."""
+    the fast level (COMPRESS_FAST), which the library refuses together with split or fse_tables.  records=True: the records level
+    (COMPRESS_RECORDS) for buffers of at most compress_record_max() bytes, one wave each; not with the three before it."""
     lens = np.array([len(b) for b in buffers], dtype=np.uint64)
     in_off = np.zeros(len(buffers), dtype=np.uint64)
     if len(buffers) > 1:
@@ -421,13 +433,14 @@ def compress_batch_host(buffers, ctx: Context, checksum: bool = False, split: bo
         out_off[1:] = np.cumsum(caps[:-1])
     out = np.zeros(max(int(caps.sum()), 1), dtype=np.uint8)
     res = ctx.compress_batch_host(in_base, in_off, lens, out_off, caps, out, checksum=checksum, split=split, fse_tables=fse_tables,
-                                  fast=fast)
+                                  fast=fast, records=records)
     return [(res[i], out[int(out_off[i]): int(out_off[i]) + int(res[i]["bytes_written"])].tobytes()) for i in range(len(buffers))]
 
 
-def compress_batch_host_dict(buffers, dict_index, ctx: Context, checksum: bool = False, dict_id: bool = True):
+def compress_batch_host_dict(buffers, dict_index, ctx: Context, checksum: bool = False, dict_id: bool = True, records: bool = False):
     """As compress_batch_host, buffer i with dictionary dict_index[i] of ctx.set_compress_dictionaries (COMPRESS_NO_DICT: none;
-    dict_index None: every buffer uses the one dictionary set): list of (result record, frame bytes)."""
+    dict_index None: every buffer uses the one dictionary set): list of (result record, frame bytes).  records=True: the records
+    level (COMPRESS_RECORDS)."""
     lens = np.array([len(b) for b in buffers], dtype=np.uint64)
     in_off = np.zeros(len(buffers), dtype=np.uint64)
     if len(buffers) > 1:
@@ -438,14 +451,15 @@ def compress_batch_host_dict(buffers, dict_index, ctx: Context, checksum: bool =
     if len(buffers) > 1:
         out_off[1:] = np.cumsum(caps[:-1])
     out = np.zeros(max(int(caps.sum()), 1), dtype=np.uint8)
-    res = ctx.compress_batch_dict_host(in_base, in_off, lens, out_off, caps, out, dict_index, checksum=checksum, dict_id=dict_id)
+    res = ctx.compress_batch_dict_host(in_base, in_off, lens, out_off, caps, out, dict_index, checksum=checksum, dict_id=dict_id, records=records)
     return [(res[i], out[int(out_off[i]): int(out_off[i]) + int(res[i]["bytes_written"])].tobytes()) for i in range(len(buffers))]
 
 
-def compress(data, ctx: Context, checksum: bool = False, split: bool = False, fse_tables: bool = False, fast: bool = False) -> bytes:
+def compress(data, ctx: Context, checksum: bool = False, split: bool = False, fse_tables: bool = False, fast: bool = False,
+             records: bool = False) -> bytes:
     """One buffer -> one zstd frame (through the batched kernel; split=True: on many workgroups when it is large; fse_tables=True:
-    per-block FSE tables for the sequences; fast=True: the fast level)."""
-    (r, frame), = compress_batch_host([data], ctx, checksum=checksum, split=split, fse_tables=fse_tables, fast=fast)
+    per-block FSE tables for the sequences; fast=True: the fast level; records=True: the records level)."""
+    (r, frame), = compress_batch_host([data], ctx, checksum=checksum, split=split, fse_tables=fse_tables, fast=fast, records=records)
     if int(r["status"]):
         raise CzError(int(r["status"]), "cz_compress_batch_host")
     return frame

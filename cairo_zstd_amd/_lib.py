@@ -28,6 +28,7 @@ COMPRESS_NO_DICT_ID = 2                 # omit the Dictionary_ID field (cz_compr
 COMPRESS_SPLIT = 4                      # cut inputs longer than compress_split_segment() into segments compressed side by side
 COMPRESS_FSE_TABLES = 16                # per-block FSE tables for the sequences where they make the block smaller
 COMPRESS_FAST = 32                      # the fast level: 32 KiB blocks that stand alone, one wave each (not with SPLIT or FSE_TABLES)
+COMPRESS_RECORDS = 64                   # the records level: one wave per record of at most compress_record_max(), with or without dictionaries
 COMPRESS_NO_DICT = 0xFFFFFFFF           # dict_index entry: no dictionary for this buffer
 
 
@@ -49,7 +50,7 @@ class BlockHeader(C.Structure):
 
 def build(force: bool = False) -> str:
     """Compile the library in-tree with hipcc for gfx950 (csrc/Makefile)."""
-    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_enc.hip", "czstd_encsplit.hip", "czstd_encfse.hip", "czstd_types.h", "czstd_dict.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_enc.hip", "czstd_encsplit.hip", "czstd_encfse.hip", "czstd_encfast.hip", "czstd_encrec.hip", "czstd_train.hip", "czstd_types.h", "czstd_dict.h")]
     srcs += [os.path.join(_HERE, "..", "include", f) for f in ("cairo_zstd_amd.h", "cairo_zstd_amd_status.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -152,6 +153,9 @@ def lib() -> C.CDLL:
     L.cz_decode_batch_host.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp]
     L.cz_compress_bound.restype = C.c_uint64
     L.cz_compress_bound.argtypes = [C.c_uint64]
+    if hasattr(L, "cz_compress_record_max"):                            # (diagnostic builds of earlier sources lack it)
+        L.cz_compress_record_max.restype = C.c_uint64
+        L.cz_compress_record_max.argtypes = []
     if hasattr(L, "cz_compress_split_segment"):                         # (diagnostic builds of earlier sources lack it)
         L.cz_compress_split_segment.restype = C.c_uint64
         L.cz_compress_split_segment.argtypes = []

@@ -112,6 +112,7 @@ __device__ static inline uint32_t cze_hash(uint32_t key) { return (key * 2654435
 
 /* Frames with a dictionary see one sequence of virtual positions: content byte v is v, input byte p is D + p. */
 __device__ static inline uint32_t cze_vb(const uint8_t* dct, uint32_t D, const uint8_t* in, uint32_t x) { return x < D ? dct[x] : in[x - D]; }
+template <int USER = 0>
 __device__ static inline uint32_t cze_vld4(const uint8_t* dct, uint32_t D, const uint8_t* in, uint32_t x) {
     if (x + 4 <= D) return cze_ld4(dct + x);
     if (x >= D) return cze_ld4(in + (x - D));
@@ -120,13 +121,14 @@ __device__ static inline uint32_t cze_vld4(const uint8_t* dct, uint32_t D, const
     return v;
 }
 /* match length at input position p against the virtual position c < D: measured against the content, across its end into the
-   input; 0 when the first 4 bytes differ, at most CZE_CAP */
+   input; 0 when the first 4 bytes differ, at most CZE_CAP.  USER (here, for cze_vld4 and for cze_match): as for cze_sequences. */
+template <int USER = 0>
 __device__ static uint32_t cze_dmatch(const uint8_t* dct, uint32_t D, const uint8_t* in, uint32_t p, uint32_t c, uint32_t lim) {
-    if (cze_ld4(in + p) != cze_vld4(dct, D, in, c)) return 0;
+    if (cze_ld4(in + p) != cze_vld4<USER>(dct, D, in, c)) return 0;
     uint32_t len = 4;
     const uint32_t cap = lim - p < CZE_CAP ? lim - p : CZE_CAP;
     while (len + 4 <= cap) {
-        const uint32_t x = cze_ld4(in + p + len) ^ cze_vld4(dct, D, in, c + len);
+        const uint32_t x = cze_ld4(in + p + len) ^ cze_vld4<USER>(dct, D, in, c + len);
         if (x) return len + ((uint32_t)__builtin_ctz(x) >> 3);
         len += 4;
     }
@@ -135,6 +137,7 @@ __device__ static uint32_t cze_dmatch(const uint8_t* dct, uint32_t D, const uint
 }
 
 /* match length at p against c < p, both in [0, lim): 0 when the first 4 bytes differ, at most CZE_CAP */
+template <int USER = 0>
 __device__ static uint32_t cze_match(const uint8_t* in, uint32_t p, uint32_t c, uint32_t lim) {
     if (cze_ld4(in + p) != cze_ld4(in + c)) return 0;
     uint32_t len = 4;

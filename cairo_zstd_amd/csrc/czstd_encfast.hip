@@ -17,7 +17,9 @@
  * two buffers of the slot, so the waves start on the next group without a second barrier.
  *
  * The frame bytes depend only on the input bytes and the flags.  Included behind czstd_encfse.hip; uses the lane-level helpers of
- * czstd_enc.hip and nothing of its shared structs, so the kernels in front of it compile as they did without it.
+ * czstd_enc.hip and nothing of its shared structs, so the kernels in front of it compile as they did without it.  USER: a copy of a
+ * wave-level function of its own for the kernels of czstd_encrec.hip (as for cze_sequences), so that this file's kernel compiles as it
+ * did without them.
  */
 #define CZQ_SUB (32u * 1024u)
 #define CZQ_GROUP CZE_BLOCK
@@ -76,6 +78,7 @@ __device__ static inline uint32_t czq_states(int v) { return v == -1 ? 1u : (uin
 
 /* all threads, once per kernel: the Predefined encode tables (RFC 8878 §3.1.1.3.2.2) — fstate[cumul[s] + rank] = the decoder state
    of that rank of symbol s, per symbol deltaFindState and deltaNbBits, and the lowest state, in which a stream may start */
+template <int USER = 0>
 __device__ static void czq_predefined() {
     const uint32_t t = threadIdx.x;
     if (t < 3) cze_fse_spread(czq_norm(t), czq_nsym(t), czq_log(t), czq.spread[t]);
@@ -125,6 +128,7 @@ __device__ static inline void czq_or(uint32_t* W, uint32_t o, uint64_t v, uint32
 /* ------------------------------------------------------------------ Huffman (a wave's own) */
 /* one lane: code lengths from the ranked symbols (two-queue Huffman tree), limited to 11 bits, and the canonical codes as the
    decoder assigns them (RFC 8878 §4.2.1).  S.sorted[0..n) holds the used symbols by ascending count; S.hlen is zero. */
+template <int USER = 0>
 __device__ static void czq_huf_build(CzqWave& S, uint32_t n) {
     for (uint32_t i = 0; i < n; i++) S.u.t.tfreq[i] = (uint16_t)S.v.hist[S.sorted[i]];
     uint32_t li = 0, ni = n, nn = n;
@@ -164,6 +168,7 @@ __device__ static inline uint32_t czq_hw(const CzqWave& S, uint32_t s) { const u
 /* one lane: the tree description (weights of symbols 0 .. last-1) into S.desc; direct 4-bit form up to 128 weights, FSE-compressed
    otherwise (accuracy log 6, two interleaved states).  Returns 0 when it cannot be written (the block then keeps raw literals).
    The weights' table takes the place of the histogram, which nobody reads any more. */
+template <int USER = 0>
 __device__ static int czq_huf_desc(CzqWave& S) {
     uint32_t last = 255;
     while (!S.hlen[last]) last--;
@@ -237,6 +242,7 @@ __device__ static int czq_huf_desc(CzqWave& S) {
 
 /* the wave: one Huffman stream of lit[s0, s1) into the words W, last literal first, four literals per lane and step; returns its
    bytes (every lane) */
+template <int USER = 0>
 __device__ static uint32_t czq_huf_stream(const CzqWave& S, const uint8_t* lit, uint32_t s0, uint32_t s1, uint32_t* W) {
     const uint32_t lane = threadIdx.x & 63u, n = s1 - s0;
     const uint32_t nw = (n * CZE_HUF_MAX_BITS + 32u) / 32u + 1u;
@@ -263,6 +269,7 @@ __device__ static uint32_t czq_huf_stream(const CzqWave& S, const uint8_t* lit, 
 
 /* the wave: the literals section of lit[0, nlit) at out; returns its length (every lane).  Raw, RLE or Huffman with a tree of its
    own (1 stream below 1 KiB, else 4): the rules of cze_literals without a dictionary. */
+template <int USER = 0>
 __device__ static uint32_t czq_literals(CzqWave& S, const uint8_t* lit, uint32_t nlit, uint8_t* out, uint32_t* hufw) {
     const uint32_t lane = threadIdx.x & 63u;
     for (uint32_t s = lane; s < 256; s += 64) { S.v.hist[s] = 0; S.hlen[s] = 0; }
@@ -294,14 +301,14 @@ __device__ static uint32_t czq_literals(CzqWave& S, const uint8_t* lit, uint32_t
     }
     uint32_t huf_len = 0xFFFFFFFFu;
     if (used >= 2 && nlit >= 32) {
-        if (lane == 0) { czq_huf_build(S, used); S.huf_ok = (uint32_t)czq_huf_desc(S); }
+        if (lane == 0) { czq_huf_build<USER>(S, used); S.huf_ok = (uint32_t)czq_huf_desc<USER>(S); }
         cz_wave_sync();
         if (S.huf_ok) {
             const uint32_t four = nlit >= 1024, ns = four ? 4u : 1u, seg = four ? (nlit + 3) / 4 : nlit;
             uint32_t sb[4] = {0, 0, 0, 0}, sum = 0;
             for (uint32_t k = 0; k < ns; k++) {
                 const uint32_t s0 = k * seg, s1 = (k + 1) * seg < nlit ? (k + 1) * seg : nlit;
-                sb[k] = czq_huf_stream(S, lit, s0, s1, hufw + k * CZQ_HUF_REGION_WORDS);
+                sb[k] = czq_huf_stream<USER>(S, lit, s0, s1, hufw + k * CZQ_HUF_REGION_WORDS);
                 sum += sb[k];
             }
             const uint32_t dl = S.desc_len, body = dl + (four ? 6u : 0u) + sum;
@@ -347,6 +354,7 @@ __device__ static inline uint32_t czq_offset_value(const CzqSeq* sq, uint32_t k,
 }
 /* the wave: the sequences section of n sequences at out[0, lim), Predefined tables; returns its length, or lim + 1 when it does not
    fit (every lane).  W: a zeroable word buffer of at least lim + 16 bytes. */
+template <int USER = 0>
 __device__ static uint32_t czq_sequences(CzqWave& S, const CzqSeq* sq, uint32_t n, uint32_t nlit, uint8_t* out, uint32_t lim, uint32_t* W,
                                          uint8_t* code, uint16_t* rec) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -428,6 +436,7 @@ __device__ static uint32_t czq_sequences(CzqWave& S, const CzqSeq* sq, uint32_t 
 /* ------------------------------------------------------------------ one sub-block on one wave */
 /* The sub-block [b0, b1) of the input, b1 > b0: RLE, Compressed (its body then in blk) or Raw, whichever is smallest.  Returns
    type << 24 | body bytes (every lane). */
+template <int USER = 0>
 __device__ static __forceinline__ uint32_t czq_block(CzqWave& S, const uint8_t* in, uint32_t b0, uint32_t b1, uint8_t* slot, uint8_t* blk) {
     const uint32_t lane = threadIdx.x & 63u, bsize = b1 - b0;
     uint8_t* lit = slot + CZQ_SCR_LIT;
@@ -460,12 +469,12 @@ __device__ static __forceinline__ uint32_t czq_block(CzqWave& S, const uint8_t* 
         uint32_t mlen = 0, moff = 0;
         if (valid) {
             for (int j = (int)lane - 1; j >= 0; j--) if (S.u.c.chash[j] == h) {
-                const uint32_t m = cze_match(in, p, c0 + (uint32_t)j, b1);
+                const uint32_t m = cze_match<USER>(in, p, c0 + (uint32_t)j, b1);
                 if (m >= 4) { mlen = m; moff = lane - (uint32_t)j; }
                 break;
             }
             if (!mlen && old) {
-                const uint32_t m = cze_match(in, p, b0 + old - 1, b1);
+                const uint32_t m = cze_match<USER>(in, p, b0 + old - 1, b1);
                 if (m >= 4) { mlen = m; moff = p - (b0 + old - 1); }
             }
         }
@@ -517,9 +526,9 @@ __device__ static __forceinline__ uint32_t czq_block(CzqWave& S, const uint8_t* 
         }
     }
     cz_wave_sync();
-    const uint32_t lsz = czq_literals(S, lit, nlit, blk, hufw);
+    const uint32_t lsz = czq_literals<USER>(S, lit, nlit, blk, hufw);
     if (lsz < bsize) {
-        const uint32_t csize = lsz + czq_sequences(S, seqs, nseq, nsl, blk + lsz, bsize - lsz, hufw, slot + CZQ_SCR_CODE, (uint16_t*)(slot + CZQ_SCR_REC));
+        const uint32_t csize = lsz + czq_sequences<USER>(S, seqs, nseq, nsl, blk + lsz, bsize - lsz, hufw, slot + CZQ_SCR_CODE, (uint16_t*)(slot + CZQ_SCR_REC));
         if (csize < bsize) return (2u << 24) | csize;
     }
     return bsize;

@@ -35,6 +35,7 @@
 #include "czstd_encsplit.hip" /* cz_compress_plan_kernel, cz_compress_segments_kernel (CZ_COMPRESS_SPLIT) */
 #include "czstd_encfse.hip"   /* cz_compress_frames_fse_kernel, cz_compress_segments_fse_kernel (CZ_COMPRESS_FSE_TABLES) */
 #include "czstd_encfast.hip"  /* cz_compress_frames_fast_kernel (CZ_COMPRESS_FAST) */
+#include "czstd_encrec.hip"   /* cz_compress_records_kernel, cz_compress_records_dict_kernel (CZ_COMPRESS_RECORDS) */
 #include "czstd_train.hip"    /* cz_train_*_kernel (cz_dictionary_train_*) */
 #ifdef CZ_EXP_PAD   /* diagnostic: shifts the code objects behind it by CZ_EXP_PAD x 256 bytes (does the layout of the kernels in the code object matter?) */
 extern "C" __global__ void cz_pad_kernel(uint32_t* p) {
@@ -113,6 +114,9 @@ struct cz_context {
     uint8_t* encfs_scratch = nullptr; int encfs_slots = 0; int encfs_grid = 0;
     /* CZ_COMPRESS_FAST: the scratch of cz_compress_frames_fast_kernel (a slot per wave), allocated by the first call that sets the flag */
     uint8_t* encq_scratch = nullptr; int encq_slots = 0; int encq_grid = 0;
+    /* CZ_COMPRESS_RECORDS: the scratch of cz_compress_records_kernel and cz_compress_records_dict_kernel (a slot per wave), allocated
+       by the first call that sets the flag; the grid of each */
+    uint8_t* encr_scratch = nullptr; int encr_slots = 0; int encr_grid = 0; int encr_dgrid = 0;
     cze_dict_entry* enc_dicts = nullptr; uint32_t enc_dict_count = 0; int enc_dgrid = 0;   /* cz_context_set_compress_dictionaries */
     float train_ms[4] = {0.f, 0.f, 0.f, 0.f};                           /* cz_dictionary_train_last_ms */
     /* staging for cz_decode_batch_host */
@@ -212,6 +216,7 @@ CZ_EXPORT void cz_context_destroy(cz_context* c) {
     if (c->encf_scratch) (void)hipFree(c->encf_scratch);
     if (c->encfs_scratch) (void)hipFree(c->encfs_scratch);
     if (c->encq_scratch) (void)hipFree(c->encq_scratch);
+    if (c->encr_scratch) (void)hipFree(c->encr_scratch);
     if (c->enc_dicts) (void)hipFree(c->enc_dicts);
     if (c->work_counter) (void)hipFree(c->work_counter);
     if (c->d_stage) (void)hipFree(c->d_stage);
@@ -1083,10 +1088,50 @@ static int cz_compress_fast_launch(cz_context* c, const void* d_in_base, const u
     return CZ_OK;
 }
 
-/* the flags cz_compress_batch_device / _host take: CZ_COMPRESS_FAST goes with the checksum alone */
+CZ_EXPORT uint64_t cz_compress_record_max(void) { return CZR_MAX; }
+
+/* CZ_COMPRESS_RECORDS: cz_compress_records_kernel or, with `dd`, cz_compress_records_dict_kernel: persistent workgroups whose waves
+   claim the records one by one, on a scratch of their own (a slot per wave of every workgroup) */
+static int cz_compress_records_launch(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
+                                      void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
+                                      const cz_enc_dargs* dd, cz_compress_result* d_results) {
+    int& kgrid = dd ? c->encr_dgrid : c->encr_grid;
+    if (!kgrid) {
+        int occ = 0;
+        const hipError_t e = dd ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_records_dict_kernel, CZE_THREADS, 0)
+                                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_records_kernel, CZE_THREADS, 0);
+        if (e != hipSuccess || occ <= 0) occ = 1;
+        kgrid = c->num_cu * occ;
+    }
+    const size_t groups = (n + CZE_WAVES - 1) / CZE_WAVES;              /* a wave per record */
+    const int grid = (size_t)kgrid < groups ? kgrid : (int)groups;
+    if (c->encr_slots < grid) {
+        if (c->encr_scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->encr_scratch); c->encr_scratch = nullptr; c->encr_slots = 0; }
+        CZ_HIP(c, hipMalloc((void**)&c->encr_scratch, (size_t)grid * CZE_RECORDS_SCRATCH_BYTES));
+        c->encr_slots = grid;
+    }
+    if (!c->enc_counter) CZ_HIP(c, hipMalloc((void**)&c->enc_counter, 64));
+    CZ_HIP(c, hipMemsetAsync(c->enc_counter, 0, 4, c->stream));
+    cz_enc_args a; memset(&a, 0, sizeof a);
+    a.in_base = (const uint8_t*)d_in_base; a.in_off = d_in_off; a.in_len = d_in_len;
+    a.out_base = (uint8_t*)d_out_base; a.out_off = d_out_off; a.out_cap = d_out_cap; a.results = d_results;
+    a.n = (uint32_t)n; a.flags = flags; a.work_counter = c->enc_counter; a.scratch = c->encr_scratch; a.scratch_stride = CZE_RECORDS_SCRATCH_BYTES;
+    if (dd) hipLaunchKernelGGL(cz_compress_records_dict_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, a, *dd);
+    else hipLaunchKernelGGL(cz_compress_records_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, a);
+    CZ_HIP(c, hipGetLastError());
+    c->last_grid = grid;
+    return CZ_OK;
+}
+
+/* the flags cz_compress_batch_device / _host take: CZ_COMPRESS_FAST and CZ_COMPRESS_RECORDS each go with the checksum alone */
 static bool cz_compress_flags_ok(uint32_t flags) {
-    if (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_SPLIT | CZ_COMPRESS_FSE_TABLES | CZ_COMPRESS_FAST)) return false;
+    if (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_SPLIT | CZ_COMPRESS_FSE_TABLES | CZ_COMPRESS_FAST | CZ_COMPRESS_RECORDS)) return false;
+    if ((flags & CZ_COMPRESS_RECORDS) && (flags & (CZ_COMPRESS_SPLIT | CZ_COMPRESS_FSE_TABLES | CZ_COMPRESS_FAST))) return false;
     return !(flags & CZ_COMPRESS_FAST) || !(flags & (CZ_COMPRESS_SPLIT | CZ_COMPRESS_FSE_TABLES));
+}
+/* ... and cz_compress_batch_dict_device / _host */
+static bool cz_compress_dict_flags_ok(uint32_t flags) {
+    return !(flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_NO_DICT_ID | CZ_COMPRESS_RECORDS));
 }
 
 CZ_EXPORT int cz_compress_batch_device(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
@@ -1099,6 +1144,7 @@ CZ_EXPORT int cz_compress_batch_device(cz_context* c, const void* d_in_base, con
     if (flags & CZ_COMPRESS_SPLIT) return cz_compress_split_launch(c, d_in_base, d_in_off, d_in_len, n, d_out_base, d_out_off, d_out_cap, flags, d_results);
     if (flags & CZ_COMPRESS_FSE_TABLES) return cz_compress_fse_launch(c, d_in_base, d_in_off, d_in_len, n, d_out_base, d_out_off, d_out_cap, flags, d_results);
     if (flags & CZ_COMPRESS_FAST) return cz_compress_fast_launch(c, d_in_base, d_in_off, d_in_len, n, d_out_base, d_out_off, d_out_cap, flags, d_results);
+    if (flags & CZ_COMPRESS_RECORDS) return cz_compress_records_launch(c, d_in_base, d_in_off, d_in_len, n, d_out_base, d_out_off, d_out_cap, flags, nullptr, d_results);
     if (!c->enc_grid) {                                                 /* workgroups of ~80 KB of LDS: as many as fit on every CU */
         int occ = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_frames_kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
@@ -1203,11 +1249,16 @@ CZ_EXPORT int cz_context_set_compress_dictionaries(cz_context* c, const cz_dicti
 CZ_EXPORT int cz_compress_batch_dict_device(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                                             void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                                             const uint32_t* d_dict_index, cz_compress_result* d_results) {
-    if (!c || (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_NO_DICT_ID)) || n > 0xFFFFFFFFull) return CZ_E_INVALID_ARG;
+    if (!c || !cz_compress_dict_flags_ok(flags) || n > 0xFFFFFFFFull) return CZ_E_INVALID_ARG;
     if (!d_dict_index && c->enc_dict_count != 1) return CZ_E_INVALID_ARG;
     if (n == 0) return CZ_OK;
     if (!d_in_base || !d_in_off || !d_in_len || !d_out_base || !d_out_off || !d_out_cap || !d_results) return CZ_E_INVALID_ARG;
     CZ_HIP(c, hipSetDevice(c->device));
+    if (flags & CZ_COMPRESS_RECORDS) {
+        cz_enc_dargs rd; memset(&rd, 0, sizeof rd);
+        rd.dicts = c->enc_dicts; rd.dict_index = d_dict_index; rd.ndicts = c->enc_dict_count;
+        return cz_compress_records_launch(c, d_in_base, d_in_off, d_in_len, n, d_out_base, d_out_off, d_out_cap, flags, &rd, d_results);
+    }
     if (!c->enc_dgrid) {
         int occ = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_frames_dict_kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
@@ -1230,7 +1281,7 @@ CZ_EXPORT int cz_compress_batch_dict_device(cz_context* c, const void* d_in_base
 CZ_EXPORT int cz_compress_batch_dict_host(cz_context* c, const void* in_base, size_t in_bytes, const uint64_t* in_off, const uint64_t* in_len, size_t n,
                                           void* out_base, size_t out_bytes, const uint64_t* out_off, const uint64_t* out_cap, uint32_t flags,
                                           const uint32_t* dict_index, cz_compress_result* results) {
-    if (!c || (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_NO_DICT_ID))) return CZ_E_INVALID_ARG;
+    if (!c || !cz_compress_dict_flags_ok(flags)) return CZ_E_INVALID_ARG;
     if (!dict_index && c->enc_dict_count != 1) return CZ_E_INVALID_ARG;
     if (n == 0) return CZ_OK;
     return cz_compress_staged(c, in_base, in_bytes, in_off, in_len, n, out_base, out_bytes, out_off, out_cap, dict_index, results,

@@ -486,6 +486,25 @@ uint64_t cz_compress_split_segment(void);   /* the segment size S in bytes */
  * are left for later.
  */
 #define CZ_COMPRESS_FAST 32u
+/*
+ * CZ_COMPRESS_RECORDS: the records level, for batches of very many small buffers, with or without dictionaries.
+ * Every wave of the device takes a whole record and writes its whole frame; an input may be at most cz_compress_record_max() =
+ * 32 KiB.  A longer one fails alone with CZ_E_INVALID_ARG: 0 bytes read and written, 0 blocks, its output region untouched.  The
+ * frame header, the optional checksum and the limits are as without the flag (in cz_compress_batch_dict_* the Dictionary_ID rules
+ * too); the frame has ONE block, Raw, RLE or Compressed, whichever is smallest (below 16 bytes: Raw or RLE; an empty input: one
+ * empty last Raw block), so cz_compress_bound holds.  The bytes depend on the input, the dictionary and the flags alone.
+ *   Without a dictionary (cz_compress_batch_device / _host, or CZ_COMPRESS_NO_DICT) the frame is byte for byte the CZ_COMPRESS_FAST
+ * frame of the same input, and status, blocks, bytes_read and bytes_written are equal too.
+ *   With a dictionary the matches come from the record itself (a table of 2^12 entries) and from the dictionary's content through
+ * its prepared table, which is read where it lies and not copied; offsets reach 1 MiB.  The literals are Raw, RLE, Huffman or
+ * Treeless with the dictionary's code, and each of LL / OF / ML is in Repeat_Mode with the dictionary's table when that has a state
+ * for every code of the block, else Predefined.  The dictionary's three repeat offsets are not referred to.
+ * Flags: in cz_compress_batch_device / _host alone or with CZ_COMPRESS_CHECKSUM; in cz_compress_batch_dict_* with
+ * CZ_COMPRESS_CHECKSUM and / or CZ_COMPRESS_NO_DICT_ID.  CZ_E_INVALID_ARG together with CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES or
+ * CZ_COMPRESS_FAST.  The result flags carry the bit whenever it was requested.  The value is 64: 8 stays an unknown bit.
+ */
+#define CZ_COMPRESS_RECORDS 64u
+uint64_t cz_compress_record_max(void);   /* 32768: the largest input CZ_COMPRESS_RECORDS takes */
 /* One per buffer, written by the device. */
 typedef struct cz_compress_result {
     int32_t  status;            /* CZ_OK | CZ_E_OUTPUT_TOO_SMALL | CZ_E_INVALID_ARG (an input of 4 GiB - 1 MiB or more) | CZ_E_WAIT_EXPIRED */
@@ -498,8 +517,8 @@ typedef struct cz_compress_result {
 /* Compresses in_base[in_off[i] .. +in_len[i]) into out_base[out_off[i] .. +out_cap[i]) for every i < n.  DEVICE pointers
  * (results too); asynchronous on the context stream; no alignment required.  A frame that fails leaves its neighbours and
  * every byte of its own region past bytes_written untouched.  out_cap[i] = cz_compress_bound(in_len[i]) always suffices.
- * flags: CZ_COMPRESS_CHECKSUM, CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES, CZ_COMPRESS_FAST (not with the two before it); any other
- * bit is CZ_E_INVALID_ARG. */
+ * flags: CZ_COMPRESS_CHECKSUM, CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES, CZ_COMPRESS_FAST (not with the two before it),
+ * CZ_COMPRESS_RECORDS (not with the three before it); any other bit is CZ_E_INVALID_ARG. */
 int cz_compress_batch_device(cz_context* ctx, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                              void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                              cz_compress_result* d_results);
@@ -528,8 +547,8 @@ int cz_context_set_compress_dictionaries(cz_context* ctx, const cz_dictionary* c
  * CZ_COMPRESS_NO_DICT (the frame then comes out byte for byte as from cz_compress_batch_device).  Any other index >= k fails that
  * frame alone with CZ_E_INVALID_ARG (nothing written), as does a dictionary content plus input of 4 GiB - 1 MiB or more.
  * d_dict_index (DEVICE, n entries) may be NULL when exactly one dictionary is set: every frame uses it.  flags: CZ_COMPRESS_CHECKSUM,
- * CZ_COMPRESS_NO_DICT_ID (CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES and CZ_COMPRESS_FAST are CZ_E_INVALID_ARG here: split frames take
- * no dictionary, dictionary frames no tables of their own, and the fast level has no dictionary kernel yet). */
+ * CZ_COMPRESS_NO_DICT_ID, CZ_COMPRESS_RECORDS (CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES and CZ_COMPRESS_FAST are CZ_E_INVALID_ARG here: split frames take
+ * no dictionary, dictionary frames no tables of their own, and the fast level has no dictionary kernel: CZ_COMPRESS_RECORDS is that level for records of at most 32 KiB). */
 int cz_compress_batch_dict_device(cz_context* ctx, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                                   void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                                   const uint32_t* d_dict_index, cz_compress_result* d_results);
