@@ -22,6 +22,7 @@
 #include <queue>
 #include <system_error>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -80,6 +81,10 @@ struct cz_dictionary {
     uint32_t id = 0; uint32_t hist[3] = {0, 0, 0};
     CzeDict* d_enc = nullptr;               /* prepared for compression (cz_enc_dict_prep_kernel) by the first cz_context_set_compress_dictionaries */
 };
+/* One scratch of the compress kernels: `slots` workgroups' worth, and per kernel that runs on it (the second: the kernel with
+   dictionaries) as many workgroups as the device holds at once, asked of the occupancy API on first use. */
+struct cz_enc_level { uint8_t* scratch = nullptr; int slots = 0; int grid[2] = {0, 0}; };
+enum { CZ_ENC_PLAIN, CZ_ENC_SPLIT, CZ_ENC_FSE, CZ_ENC_SPLIT_FSE, CZ_ENC_FAST, CZ_ENC_RECORDS, CZ_ENC_LEVELS };
 struct cz_context {
     int device = 0;
     hipStream_t stream = nullptr; bool own_stream = false;
@@ -102,22 +107,12 @@ struct cz_context {
     uint32_t* fallback_list = nullptr;                                  /* n entries, allocated with frame_first */
     int last_grid = 0;
     int last_hip_error = 0, last_hip_line = 0;
-    /* batched compression (cz_compress_batch_*): per-workgroup scratch of cz_compress_frames_kernel, allocated by the first call */
-    uint8_t* enc_scratch = nullptr; int enc_slots = 0; uint32_t* enc_counter = nullptr; int enc_grid = 0;
-    /* CZ_COMPRESS_SPLIT: the larger per-workgroup scratch of cz_compress_segments_kernel; unit_base (n + 1) and the per-frame state
-       (2 n) in one allocation sized from n; the unit counter */
-    uint8_t* encs_scratch = nullptr; int encs_slots = 0; unsigned long long* encs_plan = nullptr; size_t encs_frames = 0;
-    unsigned long long* encs_counter = nullptr; int encs_grid = 0;
-    /* CZ_COMPRESS_FSE_TABLES: the scratch of cz_compress_frames_fse_kernel and of cz_compress_segments_fse_kernel (each that of the
-       kernel it extends plus the codes and chain records), allocated by the first call that sets the flag */
-    uint8_t* encf_scratch = nullptr; int encf_slots = 0; int encf_grid = 0;
-    uint8_t* encfs_scratch = nullptr; int encfs_slots = 0; int encfs_grid = 0;
-    /* CZ_COMPRESS_FAST: the scratch of cz_compress_frames_fast_kernel (a slot per wave), allocated by the first call that sets the flag */
-    uint8_t* encq_scratch = nullptr; int encq_slots = 0; int encq_grid = 0;
-    /* CZ_COMPRESS_RECORDS: the scratch of cz_compress_records_kernel and cz_compress_records_dict_kernel (a slot per wave), allocated
-       by the first call that sets the flag; the grid of each */
-    uint8_t* encr_scratch = nullptr; int encr_slots = 0; int encr_grid = 0; int encr_dgrid = 0;
-    cze_dict_entry* enc_dicts = nullptr; uint32_t enc_dict_count = 0; int enc_dgrid = 0;   /* cz_context_set_compress_dictionaries */
+    /* batched compression (cz_compress_batch_*): one cz_enc_level per scratch, allocated by the first call that takes the level;
+       the 32-bit work counter every level but split claims its work from */
+    cz_enc_level enc[CZ_ENC_LEVELS]; uint32_t* enc_counter = nullptr;
+    /* CZ_COMPRESS_SPLIT: unit_base (n + 1) and the per-frame state (2 n) in one allocation sized from n; the unit counter */
+    unsigned long long* encs_plan = nullptr; size_t encs_frames = 0; unsigned long long* encs_counter = nullptr;
+    cze_dict_entry* enc_dicts = nullptr; uint32_t enc_dict_count = 0;   /* cz_context_set_compress_dictionaries */
     float train_ms[4] = {0.f, 0.f, 0.f, 0.f};                           /* cz_dictionary_train_last_ms */
     /* staging for cz_decode_batch_host */
     void* d_stage = nullptr; size_t d_stage_bytes = 0;
@@ -208,15 +203,10 @@ CZ_EXPORT void cz_context_destroy(cz_context* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->lit_scratch) (void)hipFree(c->lit_scratch);
-    if (c->enc_scratch) (void)hipFree(c->enc_scratch);
+    for (cz_enc_level& l : c->enc) if (l.scratch) (void)hipFree(l.scratch);
     if (c->enc_counter) (void)hipFree(c->enc_counter);
-    if (c->encs_scratch) (void)hipFree(c->encs_scratch);
     if (c->encs_plan) (void)hipFree(c->encs_plan);
     if (c->encs_counter) (void)hipFree(c->encs_counter);
-    if (c->encf_scratch) (void)hipFree(c->encf_scratch);
-    if (c->encfs_scratch) (void)hipFree(c->encfs_scratch);
-    if (c->encq_scratch) (void)hipFree(c->encq_scratch);
-    if (c->encr_scratch) (void)hipFree(c->encr_scratch);
     if (c->enc_dicts) (void)hipFree(c->enc_dicts);
     if (c->work_counter) (void)hipFree(c->work_counter);
     if (c->d_stage) (void)hipFree(c->d_stage);
@@ -975,42 +965,41 @@ CZ_EXPORT uint64_t cz_compress_bound(uint64_t src_len) {
     return 14 + 4 + 3 * blocks + src_len;              /* largest frame header, a Raw block header per block, the checksum */
 }
 
-/* scratch and work counter of the compress kernels, sized for `grid` workgroups */
-static int cz_enc_reserve(cz_context* c, int grid) {
-    if (c->enc_slots < grid) {
-        if (c->enc_scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->enc_scratch); c->enc_scratch = nullptr; c->enc_slots = 0; }
-        CZ_HIP(c, hipMalloc((void**)&c->enc_scratch, (size_t)grid * CZE_SCRATCH_BYTES));
-        c->enc_slots = grid;
+CZ_EXPORT uint64_t cz_compress_split_segment(void) { return CZE_SEG; }
+CZ_EXPORT uint64_t cz_compress_record_max(void) { return CZR_MAX; }
+
+/* a batch on the device, as the compress entry points take it */
+struct cz_enc_batch {
+    const void* in_base; const uint64_t* in_off; const uint64_t* in_len; void* out_base; const uint64_t* out_off; const uint64_t* out_cap;
+    cz_compress_result* results; size_t n; uint32_t flags;
+};
+
+/* as many workgroups of `kernel` as the device holds at once, asked once and kept in `cached` */
+template <typename K>
+static int cz_enc_grid(cz_context* c, int& cached, K kernel) {
+    if (!cached) {
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
+        cached = c->num_cu * occ;
     }
+    return cached;
+}
+/* the scratch of a level, grown to `grid` slots of `stride` bytes (launches in flight may still use the old one) */
+static int cz_enc_grow(cz_context* c, cz_enc_level& l, int grid, size_t stride) {
+    if (l.slots >= grid) return CZ_OK;
+    if (l.scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(l.scratch); l.scratch = nullptr; l.slots = 0; }
+    CZ_HIP(c, hipMalloc((void**)&l.scratch, (size_t)grid * stride));
+    l.slots = grid;
+    return CZ_OK;
+}
+/* the work counter of every level but split, cleared on the stream */
+static int cz_enc_counter(cz_context* c) {
     if (!c->enc_counter) CZ_HIP(c, hipMalloc((void**)&c->enc_counter, 64));
     CZ_HIP(c, hipMemsetAsync(c->enc_counter, 0, 4, c->stream));
     return CZ_OK;
 }
-
-CZ_EXPORT uint64_t cz_compress_split_segment(void) { return CZE_SEG; }
-
-/* CZ_COMPRESS_SPLIT: the plan kernel (units per frame, scanned; the host knows n only), then the persistent segment kernel on as
-   many workgroups as fit; both on the context stream.  Scratch, plan arrays and counter are kept and grown like enc_scratch. */
-static int cz_compress_split_launch(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
-                                    void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
-                                    cz_compress_result* d_results) {
-    const bool fse = flags & CZ_COMPRESS_FSE_TABLES;                    /* the host picks the kernel; each has its own scratch */
-    int& kgrid = fse ? c->encfs_grid : c->encs_grid; int& slots = fse ? c->encfs_slots : c->encs_slots;
-    uint8_t*& scratch = fse ? c->encfs_scratch : c->encs_scratch;
-    const size_t stride = fse ? CZE_FSE_SPLIT_SCRATCH_BYTES : CZE_SPLIT_SCRATCH_BYTES;
-    if (!kgrid) {
-        int occ = 0;
-        const hipError_t e = fse ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_segments_fse_kernel, CZE_THREADS, 0)
-                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_segments_kernel, CZE_THREADS, 0);
-        if (e != hipSuccess || occ <= 0) occ = 1;
-        kgrid = c->num_cu * occ;
-    }
-    const int grid = kgrid;
-    if (slots < grid) {
-        if (scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(scratch); scratch = nullptr; slots = 0; }
-        CZ_HIP(c, hipMalloc((void**)&scratch, (size_t)grid * stride));
-        slots = grid;
-    }
+/* CZ_COMPRESS_SPLIT: the plan arrays for n frames and the unit counter, kept and grown like a scratch; the counter cleared */
+static int cz_enc_split_plan(cz_context* c, size_t n) {
     if (c->encs_frames < n) {
         if (c->encs_plan) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->encs_plan); c->encs_plan = nullptr; c->encs_frames = 0; }
         CZ_HIP(c, hipMalloc((void**)&c->encs_plan, (3 * n + 1) * sizeof(unsigned long long)));
@@ -1018,106 +1007,38 @@ static int cz_compress_split_launch(cz_context* c, const void* d_in_base, const 
     }
     if (!c->encs_counter) CZ_HIP(c, hipMalloc((void**)&c->encs_counter, 64));
     CZ_HIP(c, hipMemsetAsync(c->encs_counter, 0, 8, c->stream));
-    cz_encsplit_args sa; memset(&sa, 0, sizeof sa);
-    sa.a.in_base = (const uint8_t*)d_in_base; sa.a.in_off = d_in_off; sa.a.in_len = d_in_len;
-    sa.a.out_base = (uint8_t*)d_out_base; sa.a.out_off = d_out_off; sa.a.out_cap = d_out_cap; sa.a.results = d_results;
-    sa.a.n = (uint32_t)n; sa.a.flags = flags; sa.a.scratch = scratch; sa.a.scratch_stride = stride;
-    sa.unit_base = c->encs_plan; sa.fstate = c->encs_plan + n + 1; sa.counter = c->encs_counter;
-    hipLaunchKernelGGL(cz_compress_plan_kernel, dim3(1), dim3(CZE_THREADS), 0, c->stream, d_in_len, (uint32_t)n, flags, sa.unit_base, sa.fstate);
-    CZ_HIP(c, hipGetLastError());
-    if (fse) hipLaunchKernelGGL(cz_compress_segments_fse_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, sa);
-    else hipLaunchKernelGGL(cz_compress_segments_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, sa);
-    CZ_HIP(c, hipGetLastError());
-    c->last_grid = grid;
     return CZ_OK;
 }
-
-/* CZ_COMPRESS_FSE_TABLES without CZ_COMPRESS_SPLIT: cz_compress_frames_fse_kernel, launched as cz_compress_frames_kernel is, on a
-   scratch of its own (the chain records make it larger) */
-static int cz_compress_fse_launch(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
-                                  void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
-                                  cz_compress_result* d_results) {
-    if (!c->encf_grid) {
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_frames_fse_kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
-        c->encf_grid = c->num_cu * occ;
-    }
-    const int grid = (size_t)c->encf_grid < n ? c->encf_grid : (int)n;
-    if (c->encf_slots < grid) {
-        if (c->encf_scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->encf_scratch); c->encf_scratch = nullptr; c->encf_slots = 0; }
-        CZ_HIP(c, hipMalloc((void**)&c->encf_scratch, (size_t)grid * CZE_FSE_SCRATCH_BYTES));
-        c->encf_slots = grid;
-    }
-    if (!c->enc_counter) CZ_HIP(c, hipMalloc((void**)&c->enc_counter, 64));
-    CZ_HIP(c, hipMemsetAsync(c->enc_counter, 0, 4, c->stream));
+static cz_enc_args cz_enc_fill(const cz_enc_batch& b, uint32_t* work_counter, uint8_t* scratch, size_t stride) {
     cz_enc_args a; memset(&a, 0, sizeof a);
-    a.in_base = (const uint8_t*)d_in_base; a.in_off = d_in_off; a.in_len = d_in_len;
-    a.out_base = (uint8_t*)d_out_base; a.out_off = d_out_off; a.out_cap = d_out_cap; a.results = d_results;
-    a.n = (uint32_t)n; a.flags = flags; a.work_counter = c->enc_counter; a.scratch = c->encf_scratch; a.scratch_stride = CZE_FSE_SCRATCH_BYTES;
-    hipLaunchKernelGGL(cz_compress_frames_fse_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, a);
-    CZ_HIP(c, hipGetLastError());
-    c->last_grid = grid;
-    return CZ_OK;
+    a.in_base = (const uint8_t*)b.in_base; a.in_off = b.in_off; a.in_len = b.in_len;
+    a.out_base = (uint8_t*)b.out_base; a.out_off = b.out_off; a.out_cap = b.out_cap; a.results = b.results;
+    a.n = (uint32_t)b.n; a.flags = b.flags; a.work_counter = work_counter; a.scratch = scratch; a.scratch_stride = stride;
+    return a;
 }
 
-/* CZ_COMPRESS_FAST: cz_compress_frames_fast_kernel, launched as cz_compress_frames_kernel is, on a scratch of its own (a slot per
-   wave of every workgroup) */
-static int cz_compress_fast_launch(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
-                                   void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
-                                   cz_compress_result* d_results) {
-    if (!c->encq_grid) {
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_frames_fast_kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
-        c->encq_grid = c->num_cu * occ;
+/* The launch of every compress level, on the context stream: persistent workgroups of `kernel`, as many as fit on the device
+   but no more than `cap` (there is no work for more), each with `stride` bytes of the level's scratch; they claim their work
+   from a counter.  `which` picks the kernel's grid in the level, `extra` is what the kernel takes after its cz_enc_args (the
+   dictionaries).  The segment kernels (CZ_COMPRESS_SPLIT) take a cz_encsplit_args instead: the plan kernel runs first (units per
+   frame, scanned; the host knows n only) and the units come from a counter of their own. */
+template <typename K, typename... X>
+static int cz_enc_launch(cz_context* c, const cz_enc_batch& b, cz_enc_level& l, int which, size_t stride, size_t cap, K kernel, X... extra) {
+    constexpr bool split = std::is_same<K, void (*)(cz_encsplit_args)>::value;
+    int grid = cz_enc_grid(c, l.grid[which], kernel);
+    if ((size_t)grid > cap) grid = (int)cap;
+    int st = cz_enc_grow(c, l, grid, stride); if (st) return st;
+    st = split ? cz_enc_split_plan(c, b.n) : cz_enc_counter(c); if (st) return st;
+    const cz_enc_args a = cz_enc_fill(b, split ? nullptr : c->enc_counter, l.scratch, stride);
+    if constexpr (split) {
+        cz_encsplit_args sa; memset(&sa, 0, sizeof sa);
+        sa.a = a; sa.unit_base = c->encs_plan; sa.fstate = c->encs_plan + b.n + 1; sa.counter = c->encs_counter;
+        hipLaunchKernelGGL(cz_compress_plan_kernel, dim3(1), dim3(CZE_THREADS), 0, c->stream, b.in_len, (uint32_t)b.n, b.flags, sa.unit_base, sa.fstate);
+        CZ_HIP(c, hipGetLastError());
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, sa);
+    } else {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, a, extra...);
     }
-    const int grid = (size_t)c->encq_grid < n ? c->encq_grid : (int)n;
-    if (c->encq_slots < grid) {
-        if (c->encq_scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->encq_scratch); c->encq_scratch = nullptr; c->encq_slots = 0; }
-        CZ_HIP(c, hipMalloc((void**)&c->encq_scratch, (size_t)grid * CZE_FAST_SCRATCH_BYTES));
-        c->encq_slots = grid;
-    }
-    if (!c->enc_counter) CZ_HIP(c, hipMalloc((void**)&c->enc_counter, 64));
-    CZ_HIP(c, hipMemsetAsync(c->enc_counter, 0, 4, c->stream));
-    cz_enc_args a; memset(&a, 0, sizeof a);
-    a.in_base = (const uint8_t*)d_in_base; a.in_off = d_in_off; a.in_len = d_in_len;
-    a.out_base = (uint8_t*)d_out_base; a.out_off = d_out_off; a.out_cap = d_out_cap; a.results = d_results;
-    a.n = (uint32_t)n; a.flags = flags; a.work_counter = c->enc_counter; a.scratch = c->encq_scratch; a.scratch_stride = CZE_FAST_SCRATCH_BYTES;
-    hipLaunchKernelGGL(cz_compress_frames_fast_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, a);
-    CZ_HIP(c, hipGetLastError());
-    c->last_grid = grid;
-    return CZ_OK;
-}
-
-CZ_EXPORT uint64_t cz_compress_record_max(void) { return CZR_MAX; }
-
-/* CZ_COMPRESS_RECORDS: cz_compress_records_kernel or, with `dd`, cz_compress_records_dict_kernel: persistent workgroups whose waves
-   claim the records one by one, on a scratch of their own (a slot per wave of every workgroup) */
-static int cz_compress_records_launch(cz_context* c, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
-                                      void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
-                                      const cz_enc_dargs* dd, cz_compress_result* d_results) {
-    int& kgrid = dd ? c->encr_dgrid : c->encr_grid;
-    if (!kgrid) {
-        int occ = 0;
-        const hipError_t e = dd ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_records_dict_kernel, CZE_THREADS, 0)
-                                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_records_kernel, CZE_THREADS, 0);
-        if (e != hipSuccess || occ <= 0) occ = 1;
-        kgrid = c->num_cu * occ;
-    }
-    const size_t groups = (n + CZE_WAVES - 1) / CZE_WAVES;              /* a wave per record */
-    const int grid = (size_t)kgrid < groups ? kgrid : (int)groups;
-    if (c->encr_slots < grid) {
-        if (c->encr_scratch) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->encr_scratch); c->encr_scratch = nullptr; c->encr_slots = 0; }
-        CZ_HIP(c, hipMalloc((void**)&c->encr_scratch, (size_t)grid * CZE_RECORDS_SCRATCH_BYTES));
-        c->encr_slots = grid;
-    }
-    if (!c->enc_counter) CZ_HIP(c, hipMalloc((void**)&c->enc_counter, 64));
-    CZ_HIP(c, hipMemsetAsync(c->enc_counter, 0, 4, c->stream));
-    cz_enc_args a; memset(&a, 0, sizeof a);
-    a.in_base = (const uint8_t*)d_in_base; a.in_off = d_in_off; a.in_len = d_in_len;
-    a.out_base = (uint8_t*)d_out_base; a.out_off = d_out_off; a.out_cap = d_out_cap; a.results = d_results;
-    a.n = (uint32_t)n; a.flags = flags; a.work_counter = c->enc_counter; a.scratch = c->encr_scratch; a.scratch_stride = CZE_RECORDS_SCRATCH_BYTES;
-    if (dd) hipLaunchKernelGGL(cz_compress_records_dict_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, a, *dd);
-    else hipLaunchKernelGGL(cz_compress_records_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, a);
     CZ_HIP(c, hipGetLastError());
     c->last_grid = grid;
     return CZ_OK;
@@ -1141,25 +1062,16 @@ CZ_EXPORT int cz_compress_batch_device(cz_context* c, const void* d_in_base, con
     if (n == 0) return CZ_OK;
     if (!d_in_base || !d_in_off || !d_in_len || !d_out_base || !d_out_off || !d_out_cap || !d_results) return CZ_E_INVALID_ARG;
     CZ_HIP(c, hipSetDevice(c->device));
-    if (flags & CZ_COMPRESS_SPLIT) return cz_compress_split_launch(c, d_in_base, d_in_off, d_in_len, n, d_out_base, d_out_off, d_out_cap, flags, d_results);
-    if (flags & CZ_COMPRESS_FSE_TABLES) return cz_compress_fse_launch(c, d_in_base, d_in_off, d_in_len, n, d_out_base, d_out_off, d_out_cap, flags, d_results);
-    if (flags & CZ_COMPRESS_FAST) return cz_compress_fast_launch(c, d_in_base, d_in_off, d_in_len, n, d_out_base, d_out_off, d_out_cap, flags, d_results);
-    if (flags & CZ_COMPRESS_RECORDS) return cz_compress_records_launch(c, d_in_base, d_in_off, d_in_len, n, d_out_base, d_out_off, d_out_cap, flags, nullptr, d_results);
-    if (!c->enc_grid) {                                                 /* workgroups of ~80 KB of LDS: as many as fit on every CU */
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_frames_kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
-        c->enc_grid = c->num_cu * occ;
-    }
-    const int grid = (size_t)c->enc_grid < n ? c->enc_grid : (int)n;
-    const int st = cz_enc_reserve(c, grid); if (st) return st;
-    cz_enc_args a; memset(&a, 0, sizeof a);
-    a.in_base = (const uint8_t*)d_in_base; a.in_off = d_in_off; a.in_len = d_in_len;
-    a.out_base = (uint8_t*)d_out_base; a.out_off = d_out_off; a.out_cap = d_out_cap; a.results = d_results;
-    a.n = (uint32_t)n; a.flags = flags; a.work_counter = c->enc_counter; a.scratch = c->enc_scratch; a.scratch_stride = CZE_SCRATCH_BYTES;
-    hipLaunchKernelGGL(cz_compress_frames_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, a);
-    CZ_HIP(c, hipGetLastError());
-    c->last_grid = grid;
-    return CZ_OK;
+    const cz_enc_batch b = {d_in_base, d_in_off, d_in_len, d_out_base, d_out_off, d_out_cap, d_results, n, flags};
+    cz_enc_level* const l = c->enc;                                     /* the host picks the kernel; each level has its own scratch */
+    const size_t all = ~(size_t)0, waves = (n + CZE_WAVES - 1) / CZE_WAVES;   /* split: units, not frames; records: a wave per record */
+    if ((flags & CZ_COMPRESS_SPLIT) && (flags & CZ_COMPRESS_FSE_TABLES))
+        return cz_enc_launch(c, b, l[CZ_ENC_SPLIT_FSE], 0, CZE_FSE_SPLIT_SCRATCH_BYTES, all, cz_compress_segments_fse_kernel);
+    if (flags & CZ_COMPRESS_SPLIT) return cz_enc_launch(c, b, l[CZ_ENC_SPLIT], 0, CZE_SPLIT_SCRATCH_BYTES, all, cz_compress_segments_kernel);
+    if (flags & CZ_COMPRESS_FSE_TABLES) return cz_enc_launch(c, b, l[CZ_ENC_FSE], 0, CZE_FSE_SCRATCH_BYTES, n, cz_compress_frames_fse_kernel);
+    if (flags & CZ_COMPRESS_FAST) return cz_enc_launch(c, b, l[CZ_ENC_FAST], 0, CZE_FAST_SCRATCH_BYTES, n, cz_compress_frames_fast_kernel);
+    if (flags & CZ_COMPRESS_RECORDS) return cz_enc_launch(c, b, l[CZ_ENC_RECORDS], 0, CZE_RECORDS_SCRATCH_BYTES, waves, cz_compress_records_kernel);
+    return cz_enc_launch(c, b, l[CZ_ENC_PLAIN], 0, CZE_SCRATCH_BYTES, n, cz_compress_frames_kernel);
 }
 
 /* Stages a host batch (inputs, descriptors, the caller's output buffer as it is, optional dict_index) and runs `launch` on the
@@ -1254,28 +1166,12 @@ CZ_EXPORT int cz_compress_batch_dict_device(cz_context* c, const void* d_in_base
     if (n == 0) return CZ_OK;
     if (!d_in_base || !d_in_off || !d_in_len || !d_out_base || !d_out_off || !d_out_cap || !d_results) return CZ_E_INVALID_ARG;
     CZ_HIP(c, hipSetDevice(c->device));
-    if (flags & CZ_COMPRESS_RECORDS) {
-        cz_enc_dargs rd; memset(&rd, 0, sizeof rd);
-        rd.dicts = c->enc_dicts; rd.dict_index = d_dict_index; rd.ndicts = c->enc_dict_count;
-        return cz_compress_records_launch(c, d_in_base, d_in_off, d_in_len, n, d_out_base, d_out_off, d_out_cap, flags, &rd, d_results);
-    }
-    if (!c->enc_dgrid) {
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_compress_frames_dict_kernel, CZE_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
-        c->enc_dgrid = c->num_cu * occ;
-    }
-    const int grid = (size_t)c->enc_dgrid < n ? c->enc_dgrid : (int)n;
-    const int st = cz_enc_reserve(c, grid); if (st) return st;
-    cz_enc_args a; memset(&a, 0, sizeof a);
-    a.in_base = (const uint8_t*)d_in_base; a.in_off = d_in_off; a.in_len = d_in_len;
-    a.out_base = (uint8_t*)d_out_base; a.out_off = d_out_off; a.out_cap = d_out_cap; a.results = d_results;
-    a.n = (uint32_t)n; a.flags = flags; a.work_counter = c->enc_counter; a.scratch = c->enc_scratch; a.scratch_stride = CZE_SCRATCH_BYTES;
+    const cz_enc_batch b = {d_in_base, d_in_off, d_in_len, d_out_base, d_out_off, d_out_cap, d_results, n, flags};
     cz_enc_dargs dd; memset(&dd, 0, sizeof dd);
     dd.dicts = c->enc_dicts; dd.dict_index = d_dict_index; dd.ndicts = c->enc_dict_count;
-    hipLaunchKernelGGL(cz_compress_frames_dict_kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, a, dd);
-    CZ_HIP(c, hipGetLastError());
-    c->last_grid = grid;
-    return CZ_OK;
+    if (flags & CZ_COMPRESS_RECORDS)
+        return cz_enc_launch(c, b, c->enc[CZ_ENC_RECORDS], 1, CZE_RECORDS_SCRATCH_BYTES, (n + CZE_WAVES - 1) / CZE_WAVES, cz_compress_records_dict_kernel, dd);
+    return cz_enc_launch(c, b, c->enc[CZ_ENC_PLAIN], 1, CZE_SCRATCH_BYTES, n, cz_compress_frames_dict_kernel, dd);
 }
 
 CZ_EXPORT int cz_compress_batch_dict_host(cz_context* c, const void* in_base, size_t in_bytes, const uint64_t* in_off, const uint64_t* in_len, size_t n,

@@ -5,40 +5,7 @@
  *   batch.bin : u64 n, then n x { u64 in_len, u64 out_cap, in bytes }
  *   result.bin: n x { cz_frame_result, out bytes (bytes_produced) }
  */
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <vector>
-
-thread_local emu_dim3 threadIdx;
-thread_local emu_dim3 blockIdx;
-emu_dim3 gridDim;
-emu_dim3 blockDim;
-pthread_barrier_t emu_barrier;
-pthread_barrier_t emu_wbar[EMU_MAX_WAVES];
-volatile uint64_t emu_xchg_all[EMU_MAX_WAVES][64];
-void* volatile emu_site[EMU_MAX_THREADS];
-void* volatile emu_ring[EMU_MAX_THREADS][64];
-volatile uint64_t emu_sync_count[EMU_MAX_THREADS];
-static volatile int emu_lane_done[EMU_MAX_THREADS];
-static volatile int emu_nthreads = 64;
-#include <execinfo.h>
-#include <unistd.h>
-/* watchdog: if no lane passes a barrier for 20 s, print where every lane waits and abort */
-static void* emu_watchdog(void*) {
-    uint64_t last = 0; int idle = 0;
-    for (;;) {
-        sleep(1);
-        uint64_t sum = 0; for (int i = 0; i < EMU_MAX_THREADS; i++) sum += emu_sync_count[i];
-        if (sum != last) { last = sum; idle = 0; continue; }
-        if (++idle < 20) continue;
-        fprintf(stderr, "EMU HANG: barrier sites per lane (addr2line -e emu_decode <addr>):\n");
-        for (int i = 0; i < emu_nthreads; i++) fprintf(stderr, "lane %d done=%d syncs=%llu site=%p\n", i, emu_lane_done[i], (unsigned long long)emu_sync_count[i], emu_site[i]);
-        for (int l = 0; l < 2; l++) { fprintf(stderr, "ring lane %d:", l); for (int k = 0; k < 64; k++) fprintf(stderr, " %p", emu_ring[l][(emu_sync_count[l] + 1 + k) & 63]); fprintf(stderr, "\n"); }
-        _exit(3);
-    }
-    return nullptr;
-}
+#include "emu_harness.h"
 
 #include "czstd_kernels.hip"
 #include "czstd_chain.hip"
@@ -49,24 +16,6 @@ namespace czx {
 #include "czstd_kernels.hip"
 }
 #undef CZ_EXEC_ONLY
-
-struct lane_arg { cz_batch_args a; unsigned lane, block; int which; const uint8_t* dict_raw; uint64_t dict_len; cz_device_frame_state* dict_state; uint64_t* dict_res; };
-static void* lane_main(void* p) {
-    lane_arg* la = (lane_arg*)p;
-    threadIdx.x = la->lane; blockIdx.x = la->block;
-    emu_lane_done[la->lane] = 0;
-    if (la->which == 0 || la->which == 12) cz_chain_kernel(la->a); else if (la->which == 2 || la->which == 11 || la->which == 13) czx::cz_execute_frames_kernel(la->a);
-    else if (la->which == 14) cz_wexec_kernel(la->a);
-    else if (la->which == 6) cz_dict_setup_kernel(la->dict_raw, la->dict_len, la->dict_state, la->dict_res);
-    else if (la->which == 7) cz_huf_kernel(la->a);
-    else if (la->which == 9) cz_huf1_kernel(la->a);
-    else if (la->which == 8) cz_tile_kernel(la->a);
-    else if (la->which == 10) cz_wexec_kernel(la->a);
-    else if (la->which >= 4) cz_scan_kernel(la->a);                     /* 4, 5: the two passes of the block scan */
-    else cz_decode_frames_kernel(la->a);
-    emu_lane_done[la->lane] = 1;
-    return nullptr;
-}
 
 int main(int argc, char** argv) {
     if (argc < 3) return 2;
@@ -104,8 +53,6 @@ int main(int argc, char** argv) {
         a.frame_first = frame_first.data(); a.chain_counter = &chain_counter;
         a.chain_min_nseq = getenv("EMU_CHAIN_MIN") ? (uint32_t)atoi(getenv("EMU_CHAIN_MIN")) : 0;
     }
-    { pthread_t wd; pthread_create(&wd, nullptr, emu_watchdog, nullptr); pthread_detach(wd); }
-    for (int w = 0; w < EMU_MAX_WAVES; w++) pthread_barrier_init(&emu_wbar[w], nullptr, 64);
     uint32_t exec_counter = 0; a.exec_counter = &exec_counter; a.exec_variant_force = 4;   /* (the emulator has one build of cz_execute_frames_kernel) */
     /* EMU_LIT=<bytes>: the literal / copy half of the pre-pass (cz_huf_kernel, cz_tile_kernel) with a literal arena of that many bytes */
     unsigned long long lit_top[4] = {0, 0, 0, 0}; std::vector<uint64_t> lit_first(n ? n : 1, 0); uint8_t* lit_arena = nullptr;
@@ -142,15 +89,8 @@ int main(int argc, char** argv) {
         fclose(df);
         uint8_t* dict_exact = (uint8_t*)malloc(dict_raw.size() ? dict_raw.size() : 1); memcpy(dict_exact, dict_raw.data(), dict_raw.size());
         dict_state = (cz_device_frame_state*)calloc(1, sizeof(cz_device_frame_state));
-        emu_nthreads = 64; pthread_barrier_init(&emu_barrier, nullptr, 64u);
-        std::vector<pthread_t> th(64); std::vector<lane_arg> la(64);
-        for (int l = 0; l < 64; l++) {
-            la[l].a = a; la[l].lane = (unsigned)l; la[l].block = 0; la[l].which = 6;
-            la[l].dict_raw = dict_exact; la[l].dict_len = dict_raw.size(); la[l].dict_state = dict_state; la[l].dict_res = dict_res;
-            pthread_create(&th[l], nullptr, lane_main, &la[l]);
-        }
-        for (int l = 0; l < 64; l++) pthread_join(th[l], nullptr);
-        pthread_barrier_destroy(&emu_barrier);
+        const uint64_t dict_len = dict_raw.size();
+        emu_launch(1, 64, [&] { cz_dict_setup_kernel(dict_exact, dict_len, dict_state, dict_res); });
         fprintf(stderr, "EMU_DICT: status %llu content offset %llu id %llu\n", (unsigned long long)dict_res[0], (unsigned long long)dict_res[1], (unsigned long long)dict_res[2]);
         if (dict_res[0]) return 3;
         a.dict_state = dict_state; a.dict = dict_exact + dict_res[1]; a.dict_len = dict_raw.size() - dict_res[1];
@@ -181,29 +121,27 @@ int main(int argc, char** argv) {
         if (which == 11) continue;
         if ((which == 7 || which == 8 || which == 9) && !lit_bytes) continue;
         const int nthreads = which == 7 ? CZH_THREADS : (which == 8 ? 256 : (which == 10 || which == 14 ? 64 * wx_waves : 64));
-        blockDim.x = (unsigned)nthreads;
-
         const int nblocks = which == 4 || which == 5 ? (int)((n + 63) / 64) : (which == 7 || which == 8 || which == 9 || which == 10 || which == 14 ? 1 : grid);
-        emu_nthreads = nthreads; gridDim.x = (unsigned)nblocks;
-        pthread_barrier_init(&emu_barrier, nullptr, (unsigned)nthreads);
-        for (int b = 0; b < nblocks; b++) {
-            std::vector<pthread_t> th((size_t)nthreads); std::vector<lane_arg> la((size_t)nthreads);
-            for (int l = 0; l < nthreads; l++) {
-                la[l].a = a; la[l].lane = (unsigned)l; la[l].block = (unsigned)b; la[l].which = which;
-                if (which == 4 || which == 5) la[l].a.scan_pass = (uint32_t)(which - 4);
-                if (which == 9 && huf1_all) la[l].a.chain_grid = 0x7FFFFFFFu;
-                if (emu_split) {
-                    if (which == 0) la[l].a.chain_part = 1u;
-                    if (which == 12) la[l].a.chain_part = 2u;
-                    if (which == 13) { la[l].a.early = 1u; la[l].a.exec_counter = &early_exec_counter; }
-                    if (which == 14) { la[l].a.early = 1u; la[l].a.wx_counter = &early_wx_counter; }
-                    if (which == 10 || which == 2) la[l].a.early = 2u;
-                }
-                pthread_create(&th[l], nullptr, lane_main, &la[l]);
-            }
-            for (int l = 0; l < nthreads; l++) pthread_join(th[l], nullptr);
+        cz_batch_args k = a;
+        if (which == 4 || which == 5) k.scan_pass = (uint32_t)(which - 4);   /* 4, 5: the two passes of the block scan */
+        if (which == 9 && huf1_all) k.chain_grid = 0x7FFFFFFFu;
+        if (emu_split) {
+            if (which == 0) k.chain_part = 1u;
+            if (which == 12) k.chain_part = 2u;
+            if (which == 13) { k.early = 1u; k.exec_counter = &early_exec_counter; }
+            if (which == 14) { k.early = 1u; k.wx_counter = &early_wx_counter; }
+            if (which == 10 || which == 2) k.early = 2u;
         }
-        pthread_barrier_destroy(&emu_barrier);
+        emu_launch(nblocks, nthreads, [&] {
+            if (which == 0 || which == 12) cz_chain_kernel(k);
+            else if (which == 2 || which == 13) czx::cz_execute_frames_kernel(k);
+            else if (which == 10 || which == 14) cz_wexec_kernel(k);
+            else if (which == 7) cz_huf_kernel(k);
+            else if (which == 9) cz_huf1_kernel(k);
+            else if (which == 8) cz_tile_kernel(k);
+            else if (which >= 4) cz_scan_kernel(k);
+            else cz_decode_frames_kernel(k);
+        });
     }
     if (lit_bytes) {
         unsigned long long nl = 0, np = 0; for (uint64_t i = 0; i < n; i++) { nl += lit_first[i] != 0; np += (frame_pre[i] & CZ_PRE_COUNT) != 0; }

@@ -4,124 +4,43 @@
  * lanes (four waves) at a time, a grid of two.  The batch's flags pick the kernel as the host library does:
  *     0 / CHECKSUM          cz_compress_frames_kernel            + FSE_TABLES   cz_compress_frames_fse_kernel
  *     SPLIT                 plan, cz_compress_segments_kernel    + FSE_TABLES   plan, cz_compress_segments_fse_kernel
- * Built with one-block segments and a small overlap (Makefile.encode_fse, the settings of Makefile.encode_split).  Workgroups run
+ * Built with one-block segments and a small overlap (the Makefile's DEFS, those of emu_encode_split).  Workgroups run
  * one after another, so this checks the format and the bookkeeping, not concurrency.  Every scratch block has its exact size.
  * usage: emu_encode_fse <batch.bin> <result.bin>
  *   batch.bin : u64 n, u32 flags, then n x { u64 in_len, u64 out_cap, in bytes }
  *   result.bin: u64 S, u64 W, then n x { cz_compress_result, the whole output region (out_cap bytes; 0xEE where nothing was written) }
  * Inputs sit one byte past the start of an exact-size heap block (unaligned), outputs in another exact-size block.
  */
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <vector>
-
-/* what the encoder needs that hip/hip_runtime.h lacks: atomicMax (32 bits for the hash table, 64 for the chain word) and the
-   sleep of a poll loop; the agent-scope loads and stores come from czstd_kernels.hip's CZ_EMU branch */
-template <class T> static inline T emu_atomic_max(T* p, T v) {
-    T cur = __atomic_load_n(p, __ATOMIC_SEQ_CST);
-    while (cur < v && !__atomic_compare_exchange_n(p, &cur, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {}
-    return cur;
-}
-static inline uint32_t atomicMax(uint32_t* p, uint32_t v) { return emu_atomic_max(p, v); }
-static inline unsigned long long atomicMax(unsigned long long* p, unsigned long long v) { return emu_atomic_max(p, v); }
-#define __builtin_amdgcn_s_sleep(x) ((void)sched_yield())
-#include <sched.h>
-
-thread_local emu_dim3 threadIdx;
-thread_local emu_dim3 blockIdx;
-emu_dim3 gridDim;
-emu_dim3 blockDim;
-pthread_barrier_t emu_barrier;
-pthread_barrier_t emu_wbar[EMU_MAX_WAVES];
-volatile uint64_t emu_xchg_all[EMU_MAX_WAVES][64];
-void* volatile emu_site[EMU_MAX_THREADS];
-void* volatile emu_ring[EMU_MAX_THREADS][64];
-volatile uint64_t emu_sync_count[EMU_MAX_THREADS];
-#include <unistd.h>
-/* watchdog: if no lane passes a barrier for 20 s, the run ends */
-static void* emu_watchdog(void*) {
-    uint64_t last = 0; int idle = 0;
-    for (;;) {
-        sleep(1);
-        uint64_t sum = 0; for (int i = 0; i < EMU_MAX_THREADS; i++) sum += emu_sync_count[i];
-        if (sum != last) { last = sum; idle = 0; continue; }
-        if (++idle < 20) continue;
-        fprintf(stderr, "EMU HANG\n");
-        _exit(3);
-    }
-    return nullptr;
-}
-
-#include "czstd_kernels.hip"
-#include "czstd_enc.hip"
+#define EMU_ENCODE
+#include "emu_harness.h"
 #include "czstd_encsplit.hip"
 #include "czstd_encfse.hip"
-
-struct lane_arg { cz_encsplit_args sa; int plan; unsigned lane, block; };
-static void* lane_main(void* p) {
-    lane_arg* la = (lane_arg*)p;
-    threadIdx.x = la->lane; blockIdx.x = la->block;
-    const uint32_t flags = la->sa.a.flags, fse = flags & CZ_COMPRESS_FSE_TABLES;
-    if (la->plan) cz_compress_plan_kernel(la->sa.a.in_len, la->sa.a.n, flags, la->sa.unit_base, la->sa.fstate);
-    else if (flags & CZ_COMPRESS_SPLIT) { if (fse) cz_compress_segments_fse_kernel(la->sa); else cz_compress_segments_kernel(la->sa); }
-    else if (fse) cz_compress_frames_fse_kernel(la->sa.a);
-    else cz_compress_frames_kernel(la->sa.a);
-    return nullptr;
-}
 
 int main(int argc, char** argv) {
     if (argc < 3) return 2;
     FILE* f = fopen(argv[1], "rb"); if (!f) return 2;
-    uint64_t n; uint32_t flags;
-    if (fread(&n, 8, 1, f) != 1 || fread(&flags, 4, 1, f) != 1) return 2;
-    std::vector<uint64_t> in_off(n), in_len(n), out_off(n), out_cap(n);
-    std::vector<uint8_t> in(1, 0x5A); uint64_t out_total = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        uint64_t l, c; if (fread(&l, 8, 1, f) != 1 || fread(&c, 8, 1, f) != 1) return 2;
-        in_off[i] = in.size(); in_len[i] = l; out_cap[i] = c; out_off[i] = out_total; out_total += c;
-        size_t at = in.size(); in.resize(at + l);
-        if (l && fread(in.data() + at, 1, l, f) != l) return 2;
-    }
-    fclose(f);
-    uint8_t* in_exact = (uint8_t*)malloc(in.size()); memcpy(in_exact, in.data(), in.size());
-    uint8_t* out = (uint8_t*)malloc(out_total ? out_total : 1); memset(out, 0xEE, out_total);
-    cz_compress_result* res = (cz_compress_result*)malloc((n ? n : 1) * sizeof(cz_compress_result));
-    memset(res, 0xA5, (n ? n : 1) * sizeof(cz_compress_result));          /* a record nobody writes shows up */
-    const int grid = 2, nthreads = CZE_THREADS;
-    const int split = (flags & CZ_COMPRESS_SPLIT) != 0, fse = (flags & CZ_COMPRESS_FSE_TABLES) != 0;
+    emu_batch b;
+    if (fread(&b.n, 8, 1, f) != 1 || fread(&b.flags, 4, 1, f) != 1 || !emu_read_batch(f, &b)) return 2;
+    const uint64_t n = b.n;
+    const int grid = 2;
+    const bool split = b.flags & CZ_COMPRESS_SPLIT, fse = b.flags & CZ_COMPRESS_FSE_TABLES;
     const size_t stride = split ? (fse ? CZE_FSE_SPLIT_SCRATCH_BYTES : CZE_SPLIT_SCRATCH_BYTES) : (fse ? CZE_FSE_SCRATCH_BYTES : CZE_SCRATCH_BYTES);
     uint8_t* scratch = (uint8_t*)malloc((size_t)grid * stride);
-    unsigned long long counter = 0; uint32_t counter32 = 0;
+    unsigned long long counter = 0;
     unsigned long long* plan = (unsigned long long*)malloc((3 * n + 1) * sizeof(unsigned long long));   /* exact size, not cleared */
     memset(plan, 0xA5, (3 * n + 1) * sizeof(unsigned long long));
     cz_encsplit_args sa; memset(&sa, 0, sizeof sa);
-    cz_enc_args& a = sa.a;
-    a.in_base = in_exact; a.in_off = in_off.data(); a.in_len = in_len.data();
-    a.out_base = out; a.out_off = out_off.data(); a.out_cap = out_cap.data(); a.results = res;
-    a.n = (uint32_t)n; a.flags = flags; a.scratch = scratch; a.scratch_stride = stride; a.work_counter = &counter32;
+    sa.a = emu_enc_args(b, scratch, stride);
     sa.unit_base = plan; sa.fstate = plan + n + 1; sa.counter = &counter;
-    { pthread_t wd; pthread_create(&wd, nullptr, emu_watchdog, nullptr); pthread_detach(wd); }
-    for (int w = 0; w < EMU_MAX_WAVES; w++) pthread_barrier_init(&emu_wbar[w], nullptr, 64);
-    blockDim.x = (unsigned)nthreads; gridDim.x = (unsigned)grid;
-    pthread_barrier_init(&emu_barrier, nullptr, (unsigned)nthreads);
-    for (int b = split ? -1 : 0; n && b < grid; b++) {                 /* (split: the plan kernel on one workgroup first) */
-        std::vector<pthread_t> th((size_t)nthreads); std::vector<lane_arg> la((size_t)nthreads);
-        gridDim.x = b < 0 ? 1u : (unsigned)grid;
-        for (int l = 0; l < nthreads; l++) {
-            la[l].sa = sa; la[l].plan = b < 0; la[l].lane = (unsigned)l; la[l].block = b < 0 ? 0u : (unsigned)b;
-            pthread_create(&th[l], nullptr, lane_main, &la[l]);
-        }
-        for (int l = 0; l < nthreads; l++) pthread_join(th[l], nullptr);
-    }
-    pthread_barrier_destroy(&emu_barrier);
+    if (n && split) emu_launch(1, CZE_THREADS, [&] { cz_compress_plan_kernel(sa.a.in_len, sa.a.n, sa.a.flags, sa.unit_base, sa.fstate); });
+    if (n) emu_launch(grid, CZE_THREADS, [&] {
+        if (split) { if (fse) cz_compress_segments_fse_kernel(sa); else cz_compress_segments_kernel(sa); }
+        else if (fse) cz_compress_frames_fse_kernel(sa.a);
+        else cz_compress_frames_kernel(sa.a);
+    });
     FILE* g = fopen(argv[2], "wb"); if (!g) return 2;
     { const uint64_t sw[2] = { CZE_SEG, CZE_OVERLAP }; fwrite(sw, 8, 2, g); }
-    for (uint64_t i = 0; i < n; i++) {
-        fwrite(&res[i], sizeof(cz_compress_result), 1, g);
-        fwrite(out + out_off[i], 1, out_cap[i], g);
-    }
-    fclose(g);
-    free(plan); free(scratch); free(res); free(out); free(in_exact);
+    emu_write_results(g, &b);
+    free(plan); free(scratch);
     return 0;
 }

@@ -9,75 +9,17 @@
  * EMU_DICTS=<file>[:<file>...]  the registered dictionaries;  EMU_NOID_DICT=<file>  the no-ID dictionary (optional)
  * Output regions start as 0xEE: a frame that writes nothing leaves them so (the runner reads them back with EMU_DUMP_ALL=1).
  */
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <stdlib.h>
+#include "emu_harness.h"
 #include <algorithm>
 #include <string>
-#include <vector>
-
-thread_local emu_dim3 threadIdx;
-thread_local emu_dim3 blockIdx;
-emu_dim3 gridDim;
-emu_dim3 blockDim;
-pthread_barrier_t emu_barrier;
-pthread_barrier_t emu_wbar[EMU_MAX_WAVES];
-volatile uint64_t emu_xchg_all[EMU_MAX_WAVES][64];
-void* volatile emu_site[EMU_MAX_THREADS];
-void* volatile emu_ring[EMU_MAX_THREADS][64];
-volatile uint64_t emu_sync_count[EMU_MAX_THREADS];
-static volatile int emu_nthreads = 64;
-#include <unistd.h>
-/* watchdog: if no lane passes a barrier for 20 s, the run ends */
-static void* emu_watchdog(void*) {
-    uint64_t last = 0; int idle = 0;
-    for (;;) {
-        sleep(1);
-        uint64_t sum = 0; for (int i = 0; i < EMU_MAX_THREADS; i++) sum += emu_sync_count[i];
-        if (sum != last) { last = sum; idle = 0; continue; }
-        if (++idle < 20) continue;
-        fprintf(stderr, "EMU HANG\n");
-        _exit(3);
-    }
-    return nullptr;
-}
 
 #include "czstd_kernels.hip"
 #include "czstd_chain.hip"
 #include "czstd_pre.hip"
 #include "czstd_dict.h"
 
-struct lane_arg { cz_batch_args a; unsigned lane, block; int which; const uint8_t* dict_raw; uint64_t dict_len; cz_device_frame_state* dict_state; uint64_t* dict_res; };
-static void* lane_main(void* p) {
-    lane_arg* la = (lane_arg*)p;
-    threadIdx.x = la->lane; blockIdx.x = la->block;
-    if (la->which == 0) cz_chain_kernel(la->a);
-    else if (la->which == 6) cz_dict_setup_kernel(la->dict_raw, la->dict_len, la->dict_state, la->dict_res);
-    else if (la->which == 7) cz_huf_kernel(la->a);
-    else if (la->which == 9) cz_huf1_kernel(la->a);
-    else if (la->which == 8) cz_tile_kernel(la->a);
-    else if (la->which >= 4) cz_scan_kernel(la->a);                     /* 4, 5: the two passes of the block scan */
-    else cz_decode_frames_kernel(la->a);
-    return nullptr;
-}
-
-static void run_lanes(const cz_batch_args& a, int which, int nthreads, int nblocks, lane_arg proto) {
-    blockDim.x = (unsigned)nthreads; emu_nthreads = nthreads; gridDim.x = (unsigned)nblocks;
-    pthread_barrier_init(&emu_barrier, nullptr, (unsigned)nthreads);
-    for (int b = 0; b < nblocks; b++) {
-        std::vector<pthread_t> th((size_t)nthreads); std::vector<lane_arg> la((size_t)nthreads, proto);
-        for (int l = 0; l < nthreads; l++) {
-            la[l].a = a; la[l].lane = (unsigned)l; la[l].block = (unsigned)b; la[l].which = which;
-            if (which == 4 || which == 5) la[l].a.scan_pass = (uint32_t)(which - 4);
-            pthread_create(&th[l], nullptr, lane_main, &la[l]);
-        }
-        for (int l = 0; l < nthreads; l++) pthread_join(th[l], nullptr);
-    }
-    pthread_barrier_destroy(&emu_barrier);
-}
-
 /* one dictionary as cz_dictionary_decode makes it: exact-size copy of the bytes, the state cz_dict_setup_kernel builds, its entry */
-static int load_dict(const char* path, const cz_batch_args& a, cz_dict_entry* e) {
+static int load_dict(const char* path, cz_dict_entry* e) {
     FILE* df = fopen(path, "rb"); if (!df) return 2;
     fseek(df, 0, SEEK_END); long dl = ftell(df); fseek(df, 0, SEEK_SET);
     uint8_t* raw = (uint8_t*)malloc(dl ? (size_t)dl : 1);
@@ -85,8 +27,7 @@ static int load_dict(const char* path, const cz_batch_args& a, cz_dict_entry* e)
     fclose(df);
     cz_device_frame_state* st = (cz_device_frame_state*)calloc(1, sizeof(cz_device_frame_state));
     uint64_t res[4] = {0, 0, 0, 0};
-    lane_arg proto; memset(&proto, 0, sizeof proto); proto.dict_raw = raw; proto.dict_len = (uint64_t)dl; proto.dict_state = st; proto.dict_res = res;
-    run_lanes(a, 6, 64, 1, proto);
+    emu_launch(1, 64, [&] { cz_dict_setup_kernel(raw, (uint64_t)dl, st, res); });
     fprintf(stderr, "EMU_DICT %s: status %llu content offset %llu id %llu\n", path, (unsigned long long)res[0], (unsigned long long)res[1], (unsigned long long)res[2]);
     if (res[0]) return 3;
     e->id = (uint32_t)res[2]; e->pad = 0; e->state = st; e->content = raw + res[1]; e->content_len = (uint64_t)dl - res[1];
@@ -119,15 +60,13 @@ int main(int argc, char** argv) {
     a.out_base = out; a.out_off = out_off.data(); a.out_cap = out_cap.data();
     a.results = res.data(); a.tasks = nullptr; a.n = (uint32_t)n; a.work_counter = &counter;
     a.lit_scratch = lit; a.lit_scratch_stride = CZ_WG_SCRATCH_BYTES; a.verify_checksum = getenv("EMU_VERIFY") ? (uint32_t)atoi(getenv("EMU_VERIFY")) : 1u;
-    { pthread_t wd; pthread_create(&wd, nullptr, emu_watchdog, nullptr); pthread_detach(wd); }
-    for (int w = 0; w < EMU_MAX_WAVES; w++) pthread_barrier_init(&emu_wbar[w], nullptr, 64);
     /* the table, as cz_context_set_dictionaries fills it: sorted by ID, and always at least one entry */
     std::vector<cz_dict_entry> table;
     if (const char* ds = getenv("EMU_DICTS")) {
         std::string all(ds);
         for (size_t at = 0; at <= all.size();) {
             size_t end = all.find(':', at); if (end == std::string::npos) end = all.size();
-            if (end > at) { cz_dict_entry e; const int st = load_dict(all.substr(at, end - at).c_str(), a, &e); if (st) return st; table.push_back(e); }
+            if (end > at) { cz_dict_entry e; const int st = load_dict(all.substr(at, end - at).c_str(), &e); if (st) return st; table.push_back(e); }
             at = end + 1;
         }
     }
@@ -137,7 +76,7 @@ int main(int argc, char** argv) {
     if (ndicts) memcpy(dicts, table.data(), ndicts * sizeof(cz_dict_entry));
     a.dicts = dicts; a.ndicts = ndicts;
     if (const char* nd = getenv("EMU_NOID_DICT")) {
-        cz_dict_entry e; const int st = load_dict(nd, a, &e); if (st) return st;
+        cz_dict_entry e; const int st = load_dict(nd, &e); if (st) return st;
         a.dict_state = e.state; a.dict = e.content; a.dict_len = e.content_len;
     }
     /* EMU_CHAIN=<bytes>: the FSE-chain pre-pass with an arena of that many bytes; EMU_LIT=<bytes>: the literal / copy half too */
@@ -169,14 +108,22 @@ int main(int argc, char** argv) {
     a.chain_grid = (uint32_t)grid;
     /* launches as the host library orders them with a dictionary setting (no execute stage) */
     const int order[7] = {4, 5, 0, 9, 7, 8, 1};
-    lane_arg proto; memset(&proto, 0, sizeof proto);
     for (int pi = 0; pi < 7; pi++) {
         const int which = order[pi];
         if (!arena && which != 1) continue;
         if ((which == 7 || which == 8 || which == 9) && !lit_bytes) continue;
         const int nthreads = which == 7 ? CZH_THREADS : (which == 8 ? 256 : 64);
         const int nblocks = which == 4 || which == 5 ? (int)((n + 63) / 64) : (which == 7 || which == 8 || which == 9 ? 1 : grid);
-        run_lanes(a, which, nthreads, nblocks, proto);
+        cz_batch_args k = a;
+        if (which == 4 || which == 5) k.scan_pass = (uint32_t)(which - 4);   /* 4, 5: the two passes of the block scan */
+        emu_launch(nblocks, nthreads, [&] {
+            if (which == 0) cz_chain_kernel(k);
+            else if (which == 7) cz_huf_kernel(k);
+            else if (which == 9) cz_huf1_kernel(k);
+            else if (which == 8) cz_tile_kernel(k);
+            else if (which >= 4) cz_scan_kernel(k);
+            else cz_decode_frames_kernel(k);
+        });
     }
     if (lit_bytes) {
         unsigned long long nd = 0; for (uint64_t i = 0; i < n; i++) nd += (frame_pre[i] & CZ_PRE_DONE) != 0;

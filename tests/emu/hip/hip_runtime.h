@@ -31,8 +31,7 @@ struct uint4 { uint32_t x, y, z, w; };
  * the 64 lanes of wave w (cross-lane intrinsics, wave barrier). */
 #define EMU_MAX_WAVES 16
 #define EMU_MAX_THREADS (64 * EMU_MAX_WAVES)
-extern pthread_barrier_t emu_barrier;
-extern pthread_barrier_t emu_wbar[EMU_MAX_WAVES];
+extern pthread_barrier_t emu_wbar[EMU_MAX_WAVES], emu_barrier;   /* (defined in emu_harness.h, as every global here) */
 extern volatile uint64_t emu_xchg_all[EMU_MAX_WAVES][64];
 #define emu_xchg (emu_xchg_all[threadIdx.x >> 6])
 #define EMU_LANE (threadIdx.x & 63u)
