@@ -14,7 +14,7 @@
  *   - CZC_SLOTS (10) quads per wave, four waves per CU: 40 chains per CU (LDS: 16-bit
  *     decoding tables 2.5 KB + a 512-byte bit ring per chain; 48 would fit, 40 leave 25 KB per CU to the huff0 waves (cz_huf1_kernel) that
  *     runs next to this kernel).
- *   - the 32 steps of a group are one hand-scheduled inline-asm block (czc_group_asm): the ring words
+ *   - the 32 steps of a group are one hand-scheduled inline-asm block (czc_group_asm2): the ring words
  *     of step i+1 are requested before the state bits of step i are extracted, the next table entry is
  *     loaded straight into the upper half of its register (ds_read_u16_d16_hi), and the record store,
  *     the cursor update and the record word of the next step sit in the shadow of that load.
@@ -188,11 +188,7 @@ __device__ static inline uint4 czc_load16(uintptr_t a, uintptr_t S, uintptr_t E)
  * stores issued behind the youngest prefetch load, s_waitcnt vmcnt(since) is enough (czc_pre_take).  The host pass and the
  * CPU emulator keep the pieces in CzcPre. */
 #define CZC_PF (16 / CZC_LPS)
-#ifdef CZC_EXP_NOSTORE
-#define CZC_GROUP_STORES 0u                 /* (diagnostic build without the record store: nothing to count, every top-up waits for vmcnt(0)) */
-#else
 #define CZC_GROUP_STORES (CZC_STEPS / 2u)   /* vector-memory operations one asm group issues: a 16-byte record store per two steps, by every lane */
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
 struct CzcPre { };
 #define CZC_PRE_PIECE(A0, A1, A2, A3, has, adr) do { \
@@ -308,7 +304,7 @@ __device__ static inline uint32_t czc_bits32(const CzcRole& ro, uint32_t v) {
 }
 /* One step (sequence_section_decoder.cairo:223-286, serial core) in plain C++: all 64 lanes call it
  * together.  `act`: this lane's chain takes the step; `last`: it is the block's last sequence (no
- * state update, :258); `store`: this lane writes the record.  The asm block below is this, scheduled — for
+ * state update, :258); `store`: this lane writes the record.  czc_group_asm2 below is this, scheduled — for
  * sequences of at most 32 extra bits.  This version takes any sequence (up to 16 + 16 + 31 extra bits): the record
  * of a wider one carries, instead of the 32 stream bits, the bit position of the sequence (bit 31 of the high word
  * set), and the decode kernel reads the extra bits from the bitstream itself.  Callers keep
@@ -343,107 +339,26 @@ __device__ static inline void czc_step(CzcLane& c, const CzcRole& ro, CZ_GLOBAL 
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)
-/* CZC_STEPS steps of every chain of the wave, none of them a block's last sequence.  Lanes without a live chain spin on the
- * idle entry and store into the sink.  Registers v100..v123 are scratch.  Wait states: a VGPR written by a VALU instruction is
+/* CZC_STEPS steps of every chain of the wave, none of them a block's last sequence, as one inline-asm block: czc_group_asm2, and
+ * czc_group_asm_wide for blocks with wider sequences.  Lanes without a live chain spin on the idle entry and store into the sink.
+ * Registers v100..v133 are scratch.  Wait states: a VGPR written by a VALU instruction is
  * read through DPP no sooner than two instructions later; the result of v_dot4c is read no sooner than four
  * instructions later (gfx940-family dot hazard); vcc is read no sooner than two instructions after v_cmp; a data
  * register of a store of more than 8 bytes is not written by the instruction right behind the store.
+ * The register map (the wide group's; the narrow group differs where its own comment says so):
  *   v100 n   v101 x << 16 | 64   v102 p   v103 v = E >> 22   v105 T   v106 t1   v107 t2   v108 a   v109 o
  *   v110 d   v111 hi  v112 lo  v113 xh  v114 wi   v115 ba  v116 bits  v117 A   v118 c   v[124:125] ring words 0, 1
- *   v[120:121] / v[122:123]  record (window, states) of the even / odd step, stored together after the odd one */
-#define CZC_ASM_HEAD(WIN) \
-    CZC_ASM_LGKM_E                                 /* the table entry; the ring words may still be on their way */ \
-    "v_ffbh_u32 v100, %[E]\n" \
-    "v_and_or_b32 v101, %[E], %[XM], %[K64]\n" \
-    "v_sub_u32 v102, v101, v100\n" \
-    "v_lshrrev_b32 v103, 22, %[E]\n" \
-    "v_and_b32 %[PH], 31, %[U]\n"                 /* phase of the cursor (and the second instruction between v102 and its DPP readers) */ \
-    "v_add_u32_dpp v105, v102, v102 quad_perm:[1,2,0,3] row_mask:0xf bank_mask:0xf\n" \
-    "v_and_b32_dpp v106, v102, %[M1] quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf\n" \
-    "v_and_b32_dpp v107, v102, %[M2] quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf\n" \
-    "v_add_u32_dpp v105, v102, v105 quad_perm:[2,0,1,3] row_mask:0xf bank_mask:0xf\n" \
-    "v_add3_u32 v109, v106, v107, v102\n" \
-    "s_waitcnt lgkmcnt(0)\n" \
-    "v_sub_co_u32_sdwa v110, vcc, %[PH], v105 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n"   /* phase - extra bits of the quad (byte 2 of the sum); vcc = they reach below the cursor word */ \
-    "v_alignbit_b32 " WIN ", %[W2], v125, %[PH]\n" \
-    "v_cndmask_b32 v111, %[W2], v125, vcc\n" \
-    "v_cndmask_b32 v112, v125, v124, vcc\n" \
-    "v_alignbit_b32 v113, v111, v112, v110\n" \
-    "v_bfe_u32 v116, v113, v109, v100\n" \
-    "v_lshl_or_b32 %[S], v103, v100, v116\n" \
-    "v_lshl_add_u32 v117, %[S], 1, %[TB]\n" \
-    "ds_read_u16_d16_hi %[E], v117\n"
-/* In the shadow of the table load (about 25 ns, a dozen instructions): the state word of the next record is
-   formed, the cursor moves, the records of two steps go out in one 16-byte store, the ring words of the
-   next step are requested.  Every lane stores: lanes 0..2 of a live quad the same records to the same
-   address, all others into the sink. */
-#ifdef CZC_EXP_NOSTORE   /* diagnostic builds (make exp): what the record store costs */
-#define CZC_ASM_STORE(OFF) "s_nop 0\n"
-#elif defined(CZC_EXP_SC1)   /* diagnostic: write-through record stores */
-#define CZC_ASM_STORE(OFF) "global_store_dwordx4 %[RP], v[120:123], off offset:" #OFF " sc1\n"
-#elif defined(CZC_EXP_SC01)
-#define CZC_ASM_STORE(OFF) "global_store_dwordx4 %[RP], v[120:123], off offset:" #OFF " sc0 sc1\n"
-#elif defined(CZC_EXP_NT)
-#define CZC_ASM_STORE(OFF) "global_store_dwordx4 %[RP], v[120:123], off offset:" #OFF " nt\n"
-#else
+ *   v[120:121] / v[122:123]  record (window, states) of the even / odd step, stored together after the odd one
+ * In the shadow of the table load that ends a step's head (about 25 ns, a dozen instructions) its tail forms the state word of
+ * the next record, moves the cursor, sends the records of two steps out in one 16-byte store and requests the ring words of the
+ * next step.  Every lane stores: lanes 0..2 of a live quad the same records to the same address, all others into the sink. */
 #define CZC_ASM_STORE(OFF) "global_store_dwordx4 %[RP], v[120:123], off offset:" #OFF "\n"
-#endif
 #define CZC_ASM_RING01 "ds_read2_b32 v[124:125], v115 offset1:1\n"
-#define CZC_ASM_LGKM_E "s_waitcnt lgkmcnt(2)\n"
-#define CZC_ASM_TAIL(STORE, NEXTH) \
-    STORE \
-    "v_lshl_add_u32 v118, %[S], %[SH], %[NK]\n" \
-    "v_dot4c_i32_i8_e32 %[U], 0x01ff0001, v105\n" \
-    "v_max_u32_sdwa %[SLOW], %[SLOW], v105 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n"   /* most extra bits of any step so far; also the spacer: v118 -> DPP two instructions, v_dot4c -> reader three, 16-byte store -> write of its data one */ \
-    "v_add_u32_dpp " NEXTH ", v118, v118 quad_perm:[1,2,0,3] row_mask:0xf bank_mask:0xf\n" \
-    "v_add_u32_dpp " NEXTH ", v118, " NEXTH " quad_perm:[2,0,1,3] row_mask:0xf bank_mask:0xf\n" \
-    "v_bfe_u32 v114, %[U], 5, 7\n" \
-    "v_lshl_add_u32 v115, v114, 2, %[RB]\n" \
-    CZC_ASM_RING01 \
-    "ds_read_b32 %[W2], v115 offset:8\n"
-#define CZC_ASM_EVEN(OFF) CZC_ASM_HEAD("v120") CZC_ASM_TAIL("", "v123")
-#define CZC_ASM_ODD(OFF) CZC_ASM_HEAD("v122") CZC_ASM_TAIL(CZC_ASM_STORE(OFF), "v121")
-#define CZC_ASM_PAIR(A) CZC_ASM_EVEN(A) CZC_ASM_ODD(A)
-/* `rec`: where this lane's 32 records go (lanes 0..2 of a live quad: the chain's records; every other lane: the sink) */
-__device__ static inline void czc_group_asm(CzcLane& c, const CzcRole& ro, CZ_GLOBAL uint64_t* rec) {
-    static_assert(CZC_STEPS == 32, "the asm block is unrolled for 32 steps");
-    /* ds_* instructions take the 32-bit LDS address */
-    const uint32_t tb32 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint16_t*)ro.tb;
-    const uint32_t rb32 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint8_t*)ro.ringm8;
-    /* Inside the block the state register holds state + 512: (v << num_bits) | bits keeps the marker of v at
-       bit 9, which the table base (tb32 - 1024) and the record word (nk = -(512 << sh)) absorb.
-       Per lane p = extra bits << 16 | (64 - num_bits) [| 64 << 24 on lane 0]: summed over the quad, byte 0 is
-       192 - state bits (its low 5 bits, summed over the lanes up to this one, are the v_bfe offset of this
-       lane's field counted from the top of the window), byte 2 the extra bits, byte 3 the 64 that v_dot4c
-       with weights (+1, 0, -1, +1) needs to turn byte 0 (-64 - state bits as a signed byte) into -state bits. */
-    const uint32_t tbm = tb32 - 1024u, nk = 0u - (512u << ro.sh), k64 = ro.lane0 ? 0x40000040u : 0x40u;
-    c.S += 512u;
-    asm volatile(
-        "v_mov_b32 v124, %[W0]\n"
-        "v_mov_b32 v125, %[W1]\n"
-        "v_mov_b32 v108, 0\n"
-        /* state word of the first record */
-        "v_lshl_add_u32 v118, %[S], %[SH], %[NK]\n"
-        "s_nop 1\n"
-        "v_add_u32_dpp v121, v118, v118 quad_perm:[1,2,0,3] row_mask:0xf bank_mask:0xf\n"
-        "v_add_u32_dpp v121, v118, v121 quad_perm:[2,0,1,3] row_mask:0xf bank_mask:0xf\n"
-        CZC_ASM_PAIR(0) CZC_ASM_PAIR(16) CZC_ASM_PAIR(32) CZC_ASM_PAIR(48) CZC_ASM_PAIR(64) CZC_ASM_PAIR(80) CZC_ASM_PAIR(96) CZC_ASM_PAIR(112)
-        CZC_ASM_PAIR(128) CZC_ASM_PAIR(144) CZC_ASM_PAIR(160) CZC_ASM_PAIR(176) CZC_ASM_PAIR(192) CZC_ASM_PAIR(208) CZC_ASM_PAIR(224) CZC_ASM_PAIR(240)
-        "s_waitcnt lgkmcnt(0)\n"
-        "v_and_b32 %[PH], 31, %[U]\n"
-        "v_mov_b32 %[W0], v124\n"
-        "v_mov_b32 %[W1], v125\n"
-        : [E] "+v"(c.E), [S] "+v"(c.S), [U] "+v"(c.u), [PH] "+v"(c.ph), [W0] "+v"(c.w0), [W1] "+v"(c.w1), [W2] "+v"(c.w2), [SLOW] "+v"(c.slow)
-        : [TB] "v"(tbm), [RB] "v"(rb32), [M1] "v"(ro.m1 ? 0xFFu : 0u), [M2] "v"(ro.m2 ? 0xFFu : 0u), [SH] "v"(ro.sh), [NK] "v"(nk), [K64] "v"(k64),
-          [XM] "s"(0x1F0000u), [RP] "v"(rec)
-        : "memory", "vcc",
-          "v100", "v101", "v102", "v103", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115",
-          "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125");
-    c.S -= 512u;
-}
+#define CZC_ASM_LGKM_E "s_waitcnt lgkmcnt(2)\n"   /* the table entry; the ring words may still be on their way */
 
-/* Round 5: the same 32 steps with the field picked by two 64-bit shifts instead of a compare, two selects, a funnel shift and a
- * bit-field extract — 29.5 instructions per step instead of 31.5, and a lone wave pays ~2.9 ns for every one of them
+/* The narrow group (sequences of at most 32 extra bits).  The field is picked by two 64-bit shifts, where the wide group — like the
+ * narrow one before round 5 — takes a compare, two selects, a funnel shift and a bit-field extract: 29.5 instructions per step
+ * instead of 31.5, and a lone wave pays ~2.9 ns for every one of them
  * (profiles/r5/NOTES.md section 1; scripts/micro/chain_step.hip variants 1 / 10: 74.0 -> 67.2 ns).
  *   per lane p = num_bits << 8 | extra bits (v102); summed over the quad (v105): byte 0 = the sequence's extra bits, byte 1 = its state
  *   bits; sh (v109, low 6 bits) = extra bits + state bits of the lanes before this one = where this lane's field begins, counted
@@ -487,10 +402,14 @@ __device__ static inline void czc_group_asm(CzcLane& c, const CzcRole& ro, CZ_GL
 #define CZC_ASM2_EVEN(OFF) CZC_ASM2_HEAD("v120") CZC_ASM2_TAIL("", "v123")
 #define CZC_ASM2_ODD(OFF) CZC_ASM2_HEAD("v122") CZC_ASM2_TAIL(CZC_ASM_STORE(OFF), "v121")
 #define CZC_ASM2_PAIR(A) CZC_ASM2_EVEN(A) CZC_ASM2_ODD(A)
+/* `rec`: where this lane's 32 records go (lanes 0..2 of a live quad: the chain's records; every other lane: the sink) */
 __device__ static inline void czc_group_asm2(CzcLane& c, const CzcRole& ro, CZ_GLOBAL uint64_t* rec) {
     static_assert(CZC_STEPS == 32, "the asm block is unrolled for 32 steps");
+    /* ds_* instructions take the 32-bit LDS address */
     const uint32_t tb32 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint16_t*)ro.tb;
     const uint32_t rb32 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint8_t*)ro.ringm8;
+    /* Inside the block the state register holds state + 512: (v << num_bits) | bits keeps the marker of v at
+       bit 9, which the table base (tb32 - 1024) and the record word (nk = -(512 << sh)) absorb. */
     const uint32_t tbm = tb32 - 1024u, nk = 0u - (512u << ro.sh);
     c.S += 512u;
     asm volatile(
@@ -572,6 +491,10 @@ __device__ static inline void czc_group_asm2(CzcLane& c, const CzcRole& ro, CZ_G
 __device__ static inline void czc_group_asm_wide(CzcLane& c, const CzcRole& ro, CZ_GLOBAL uint64_t* rec) {
     const uint32_t tb32 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint16_t*)ro.tb;
     const uint32_t rb32 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint8_t*)ro.ringm8 - 4u;   /* ring - 12: four words end at the cursor word */
+    /* state + 512 as in czc_group_asm2.  Per lane p = extra bits << 16 | (64 - num_bits) [| 64 << 24 on lane 0]: summed over the
+       quad, byte 0 is 192 - state bits (its low 5 bits, summed over the lanes up to this one, are the v_bfe offset of this
+       lane's field counted from the top of the window), byte 2 the extra bits, byte 3 the 64 that v_dot4c
+       with weights (+1, 0, -1, +1) needs to turn byte 0 (-64 - state bits as a signed byte) into -state bits. */
     const uint32_t tbm = tb32 - 1024u, nk = 0u - (512u << ro.sh), k64 = ro.lane0 ? 0x40000040u : 0x40u;
     c.S += 512u;
     asm volatile(
@@ -857,7 +780,7 @@ extern "C" __global__ void __launch_bounds__(CZ_WG_THREADS) cz_scan_kernel(cz_ba
         uint64_t total, incl = czs_scan64(units, &total), wbase = 0;
         if (LANE == 0 && total) wbase = atomicAdd(a.chain_top, (unsigned long long)total);
         wbase = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(wbase >> 32), 0) << 32) | (uint32_t)__shfl((int)(uint32_t)wbase, 0);
-        if (units) { at = 64ull + wbase + (incl - units); if (at + units > a.chain_capacity) { at = 0; placed = 0; } }   /* indices 0..63 are reserved: 0 = none, 8..39 = the sink of czc_group_asm */
+        if (units) { at = 64ull + wbase + (incl - units); if (at + units > a.chain_capacity) { at = 0; placed = 0; } }   /* indices 0..63 are reserved: 0 = none, 8..39 = the sink of czc_group_asm2 and czc_group_asm_wide */
     }
     if (with_lits) {
         uint64_t total, incl = czs_scan64(lbytes, &total), wbase = 0;
@@ -1282,11 +1205,7 @@ extern "C" __global__ void __launch_bounds__(CZ_WG_THREADS, 1) cz_chain_kernel(c
                 if (!any_wide) {
                     const uint32_t sv_E = c.E, sv_S = c.S; const int32_t sv_u = c.u;   /* what a redo starts from (the ring words are read again) */
                     c.slow = 0;
-#ifdef CZC_EXP_OLD_STEP
-                    czc_group_asm(c, ro, rp);
-#else
                     czc_group_asm2(c, ro, rp);
-#endif
                     since += CZC_GROUP_STORES;
                     if (czc_any(c.slow > 32)) {                         /* redo this group wide; the slots that met a wide sequence stay wide for their block */
                         const int hit = chain_live && ql < 3 && c.slow > 32;

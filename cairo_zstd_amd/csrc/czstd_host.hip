@@ -38,13 +38,6 @@
 #include "czstd_encfast.hip"  /* cz_compress_frames_fast_kernel (CZ_COMPRESS_FAST) */
 #include "czstd_encrec.hip"   /* cz_compress_records_kernel, cz_compress_records_dict_kernel (CZ_COMPRESS_RECORDS) */
 #include "czstd_train.hip"    /* cz_train_*_kernel (cz_dictionary_train_*) */
-#ifdef CZ_EXP_PAD   /* diagnostic: shifts the code objects behind it by CZ_EXP_PAD x 256 bytes (does the layout of the kernels in the code object matter?) */
-extern "C" __global__ void cz_pad_kernel(uint32_t* p) {
-#pragma unroll
-    for (int i = 0; i < CZ_EXP_PAD * 32; i++) asm volatile("s_nop 0\n s_nop 0");
-    if (p) p[0] = 1;
-}
-#endif
 /* the same kernel source once more, without its decoders: cz_execute_frames_kernel (czstd_kernels.hip, CZ_EXEC_ONLY) */
 #define CZ_EXEC_ONLY 1
 namespace czx {
@@ -67,9 +60,6 @@ namespace czx8 {
 
 #define CZ_EXPORT extern "C" __attribute__((visibility("default")))
 #define CZ_CTL_BLOCK_BYTES (192 + CZ_SCAN_CTL_WORDS * 4)
-#ifndef CZ_WX_SPARE_WGS
-#define CZ_WX_SPARE_WGS 0       /* workgroups of cz_wexec_kernel beyond those that stay */
-#endif
 
 /* ------------------------------------------------------------------ context */
 /* Dictionary (src/decoding/dictionary.cairo:11-18): the raw bytes and the carried-state image decode_dict makes of them, both
@@ -557,10 +547,7 @@ static int cz_enqueue(cz_context* c, const cz_batch_args& proto, size_t n, hipSt
     a.prof = c->d_prof; a.verify_checksum = a.tasks ? 0 : c->verify_checksum; a.debug_flags = c->debug_flags;
     if (!a.tasks && c->batch_dict) { a.dict_state = c->batch_dict->d_state; a.dict = c->batch_dict->d_raw + c->batch_dict->content_off; a.dict_len = c->batch_dict->len - c->batch_dict->content_off; }
     if (!a.tasks && c->dict_table) { a.dicts = c->dict_table; a.ndicts = c->dict_count; }
-    int grid = (int)(n < (size_t)c->grid_max ? n : (size_t)c->grid_max);
-#ifdef CZ_EXPERIMENT
-    if (const char* e = getenv("CZ_GRID_PER_CU")) { const int g = atoi(e) * c->num_cu; if (g > 0 && g < grid) grid = g; }
-#endif
+    const int grid = (int)(n < (size_t)c->grid_max ? n : (size_t)c->grid_max);
     if (c->lit_slots < grid) {                                          /* one literal scratch region per resident workgroup */
         if (cap) return CZ_E_NOGRAPH;
         c->cfg_gen++;
@@ -651,25 +638,6 @@ static int cz_enqueue(cz_context* c, const cz_batch_args& proto, size_t n, hipSt
         }
         /* the literal and copy kernels may start when the chain kernel does (not before: they would take the LDS the chain
            kernel's workgroups need and hold them up) */
-#ifdef CZ_EXPERIMENT
-        /* diagnostic (CZ_EXP_OVERLAP = workgroups per CU): what cz_execute_frames_kernel and cz_chain_kernel cost each other when they
-           run side by side.  The execute kernel works on the records the PREVIOUS launch left in the arena (same batch, same
-           bytes), after all literals; its output is the same bytes again.  Read the kernel trace, not the event times. */
-        const char* ovl = use_exec ? getenv("CZ_EXP_OVERLAP") : nullptr;
-        if (ovl) {
-            hipLaunchKernelGGL(cz_huf_kernel, dim3(c->huf_grid), dim3(CZH_THREADS), 0, s0, a);
-            CZ_HIP(c, hipEventRecord(c->ev_fork, s0));
-            CZ_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-            cz_batch_args a2 = a; a2.exec_counter = c->work_counter;
-            hipLaunchKernelGGL(czx::cz_execute_frames_kernel, dim3(atoi(ovl) * c->num_cu), dim3(CZ_WG_THREADS), CZ_EXEC_DYN_LDS, c->stream2, a2);
-            CZ_HIP(c, hipEventRecord(c->ev_join, c->stream2));
-            a.chain_grid = (uint32_t)c->chain_grid;
-            hipLaunchKernelGGL(cz_chain_kernel, dim3(c->chain_grid), dim3(CZ_WG_THREADS), 0, s0, a);
-            CZ_HIP(c, hipStreamWaitEvent(s0, c->ev_join, 0));
-            CZ_HIP(c, hipMemsetAsync(c->work_counter, 0, 4, s0));
-            CZ_HIP(c, hipEventRecord(c->ev_fork, s0));
-        }
-#endif
         if (lit_pass) CZ_HIP(c, hipEventRecord(c->ev_fork, s0));
         const int cgrid = c->chain_grid;                                /* the waves take blocks off the list until it is empty */
         a.chain_grid = (uint32_t)(split ? 2 * cgrid : cgrid);           /* (cz_huf1_kernel stops when this many chain waves have counted themselves out) */
@@ -696,11 +664,7 @@ static int cz_enqueue(cz_context* c, const cz_batch_args& proto, size_t n, hipSt
             CZ_HIP(c, hipGetLastError());
             CZ_HIP(c, hipEventRecord(c->ev_join3, c->stream3));
             CZ_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-            int h1grid = c->huf1_grid;
-#ifdef CZ_EXPERIMENT
-            if (const char* e = getenv("CZ_HUF1_PER_CU")) { const int g = atoi(e) * c->num_cu; if (g > 0) h1grid = g; }
-#endif
-            if (!(c->debug_flags & CZ_DEBUG_NO_HUF1)) hipLaunchKernelGGL(cz_huf1_kernel, dim3(h1grid), dim3(CZ_WG_THREADS), 0, c->stream2, a);
+            if (!(c->debug_flags & CZ_DEBUG_NO_HUF1)) hipLaunchKernelGGL(cz_huf1_kernel, dim3(c->huf1_grid), dim3(CZ_WG_THREADS), 0, c->stream2, a);
             CZ_HIP(c, hipGetLastError());
             CZ_HIP(c, hipEventRecord(c->ev_join, c->stream2));
             hipLaunchKernelGGL(cz_huf_kernel, dim3(c->huf_grid), dim3(CZH_THREADS), 0, sl, a);
@@ -719,10 +683,7 @@ static int cz_enqueue(cz_context* c, const cz_batch_args& proto, size_t n, hipSt
         c->timed_chain = true;
         c->timed_exec = false; c->timed_wx = false; c->timed_small = split;
         if (use_exec) {
-            int egrid = (int)(n < (size_t)c->exec_grid ? n : (size_t)c->exec_grid);
-#ifdef CZ_EXPERIMENT
-            if (const char* e = getenv("CZ_EXEC_PER_CU")) { const int g = atoi(e) * c->num_cu; if (g > 0 && g < egrid) egrid = g; }
-#endif
+            const int egrid = (int)(n < (size_t)c->exec_grid ? n : (size_t)c->exec_grid);
             const int egrid8 = (int)(n < (size_t)c->exec8_grid ? n : (size_t)c->exec8_grid);
             a.wx_leave = 0; a.exec_variant_force = c->exec_variant_force; a.wx_force = c->wexec_force;
             if (split) {
@@ -754,12 +715,11 @@ static int cz_enqueue(cz_context* c, const cz_batch_args& proto, size_t n, hipSt
                 /* (args.wx_cus workgroups of cz_wexec_kernel stay; while they are not all in place, cz_execute_frames_kernel's waves keep off the
                    even CUs — cz_cu_side —, so the split does not depend on which kernel the dispatcher places first) */
                 const int wcus = c->wexec_cus > 0 ? (c->wexec_cus > c->num_cu ? c->num_cu : c->wexec_cus) : c->num_cu / 2;
-                const int wgrid = wcus + CZ_WX_SPARE_WGS;
                 a.wx_cus = (uint32_t)wcus;
                 a.wx_leave = a.wx_cus * (uint32_t)c->wexec_leave_per_cu;
                 const bool exec_first = (c->debug_flags & CZ_DEBUG_EXEC_FIRST) != 0;   /* test knob: the other submission order */
                 if (!exec_first) {
-                    hipLaunchKernelGGL(cz_wexec_kernel, dim3(wgrid), dim3(WX_THREADS), WX_LDS_BYTES, s0, a);
+                    hipLaunchKernelGGL(cz_wexec_kernel, dim3(wcus), dim3(WX_THREADS), WX_LDS_BYTES, s0, a);
                     CZ_HIP(c, hipGetLastError());
                     CZ_HIP(c, rec_t(c->ev_wx, s0));
                 }
@@ -770,7 +730,7 @@ static int cz_enqueue(cz_context* c, const cz_batch_args& proto, size_t n, hipSt
                 CZ_HIP(c, hipEventRecord(split ? c->ev_x4 : c->ev_join, sx));
                 if (exec_first) {                                       /* (only the host's submission order: where the dispatcher places each kernel is its own affair) */
                     CZ_HIP(c, hipStreamWaitEvent(s0, cap ? c->ev_lit_dep : c->ev_lit, 0));
-                    hipLaunchKernelGGL(cz_wexec_kernel, dim3(wgrid), dim3(WX_THREADS), WX_LDS_BYTES, s0, a);
+                    hipLaunchKernelGGL(cz_wexec_kernel, dim3(wcus), dim3(WX_THREADS), WX_LDS_BYTES, s0, a);
                     CZ_HIP(c, hipGetLastError());
                     CZ_HIP(c, rec_t(c->ev_wx, s0));
                 }

@@ -95,15 +95,8 @@ __device__ static inline uint32_t cz_cu_side() {
 #if defined(CZ_EMU) || !defined(__HIP_DEVICE_COMPILE__) || !defined(__gfx950__)
     return 2u;
 #else
-#ifndef CZ_CU_SIDE_RULE
-#define CZ_CU_SIDE_RULE 0
-#endif
-    const uint32_t hw = __builtin_amdgcn_s_getreg((31u << 11) | (0u << 6) | 4u);    /* HW_REG_HW_ID (4): cu_id [11:8], se_id [15:13] */
-    const uint32_t xcc = __builtin_amdgcn_s_getreg((3u << 11) | (0u << 6) | 20u);   /* HW_REG_XCC_ID (20): [3:0] */
-    const uint32_t cu = (hw >> 8) & 15u, se = (hw >> 13) & 7u;
-    (void)xcc; (void)se; (void)cu;
-    return CZ_CU_SIDE_RULE == 0 ? (cu & 1u) ^ 1u : CZ_CU_SIDE_RULE == 1 ? (xcc & 1u) ^ 1u : CZ_CU_SIDE_RULE == 2 ? (xcc < 4u ? 1u : 0u)
-         : CZ_CU_SIDE_RULE == 3 ? (se & 1u) ^ 1u : ((cu >> 1) & 1u) ^ 1u;
+    const uint32_t hw = __builtin_amdgcn_s_getreg((31u << 11) | (0u << 6) | 4u);    /* HW_REG_HW_ID (4): cu_id [11:8] */
+    return ((hw >> 8) & 1u) ^ 1u;
 #endif
 }
 /* Agent-scope hand-off between kernels that run at the same time (the large blocks' chains -> cz_wexec_kernel's early launch).
@@ -160,13 +153,9 @@ enum { CZ_P_HDR = 0, CZ_P_HUFBUILD, CZ_P_HUFDEC, CZ_P_SEQTAB, CZ_P_RING, CZ_P_CH
    trip per dependency round (profiles/r4/NOTES.md). */
 #undef CZ_OBUF_BYTES
 #undef CZ_OBUF_MAXLEN
-#if defined(CZ_EXEC_ONLY) && CZ_EXEC_WAVES == 4 && !defined(CZ_EXP_SMALL_OBUF)
+#if defined(CZ_EXEC_ONLY) && CZ_EXEC_WAVES == 4
 #define CZ_OBUF_BYTES 3072u
-#ifdef CZ_EXP_MAXLEN
-#define CZ_OBUF_MAXLEN CZ_EXP_MAXLEN
-#else
 #define CZ_OBUF_MAXLEN 128u
-#endif
 #else
 #define CZ_OBUF_BYTES 1024u
 #define CZ_OBUF_MAXLEN 64u
@@ -1031,11 +1020,7 @@ __device__ static void cz_huf_streams_par(cz_gcptr blk, cz_gptr target, uint32_t
     int32_t ck[4] = { CK_NONE, CK_NONE, CK_NONE, CK_NONE };            /* positions the speculative pass went through */
     uint32_t ckn[4] = { 0, 0, 0, 0 };                                   /* ... and the symbols it had counted there */
     /* the passes that only count step two symbols at a time where the table says so (cz_huf_fill_multi) */
-#ifdef CZ_EXP_NO_MULTI
-#define CZ_MULTI 0
-#else
 #define CZ_MULTI 1
-#endif
     n = cz_gb_decode(g, mb, stop, live, nullptr, 0, CZ_MULTI, ck, ckn);   /* 1. speculative pass */
     if (live) e = g.p;
     CZ_PROF_ACC(CZ_P_HUF_SPEC);
@@ -1360,13 +1345,7 @@ __device__ static inline void cz_copy_long_runs(uint8_t* ob, uint8_t* stg, uint3
         const uint32_t lo = 1024u * t + 16u * (uint32_t)LANE;
         sv[t] = uint4{0, 0, 0, 0};
         if (staged && 1024u * t < sum_ll) {                              /* (uniform) */
-#if defined(CZ_EXP_LITNEAR)   /* diagnostic only (wrong output): the literals always from the start of the literal buffer (cache hits) */
-            if (lo < sum_ll) sv[t] = cz_load_upto16((cz_gcptr)lit.p + lo, sum_ll - lo < 16u ? sum_ll - lo : 16u, (uint64_t)lo + 16u <= lit.len);
-#elif defined(CZ_EXP_NOLOADS)  /* diagnostic only (wrong output): no loads at all here */
-            if (lo < sum_ll) sv[t] = uint4{lo, lo, lo, lo};
-#else
             if (lo < sum_ll) sv[t] = cz_load_upto16((cz_gcptr)lit.p + lit_used + lo, sum_ll - lo < 16u ? sum_ll - lo : 16u, (uint64_t)lit_used + lo + 16u <= lit.len);
-#endif
         }
     }
     for (uint32_t k = 0; k == 0 || __ballot(far_plain && k < ml); k += 64) {
@@ -1374,11 +1353,7 @@ __device__ static inline void cz_copy_long_runs(uint8_t* ob, uint8_t* stg, uint3
         for (uint32_t j = 0; j < 4; j++) {
             const uint32_t at = k + 16u * j;
             mv[j] = uint4{0, 0, 0, 0};
-#ifdef CZ_EXP_NOLOADS
-            if (far_plain && at < ml) mv[j] = uint4{ml, ml, ml, ml};
-#else
             if (far_plain && at < ml) mv[j] = cz_load_upto16(ms + at, ml - at < 16u ? ml - at : 16u, ms_pos + at + 16u <= cap);
-#endif
         }
         if (k == 0) {
 #pragma unroll
@@ -1395,11 +1370,7 @@ __device__ static inline void cz_copy_long_runs(uint8_t* ob, uint8_t* stg, uint3
         if (k < ll) {
             uint4 v;
             if (lit.rle) { const uint32_t w = 0x01010101u * lit.byte; v = uint4{w, w, w, w}; }
-#ifdef CZ_EXP_NOSTAGE   /* diagnostic only: the literals by their lanes from global memory, a round trip per 16 bytes (the scheme before) */
-            else v = cz_load_upto16((cz_gcptr)lit.p + lit_used + lrel + k, ll - k < 16u ? ll - k : 16u, (uint64_t)lit_used + lrel + k + 16u <= lit.len);
-#else
             else __builtin_memcpy(&v, stg + lrel + k, 16);
-#endif
             (cz_lds_store_upto16)(ob + orel + k, v, ll - k < 16u ? ll - k : 16u);
         }
     }
@@ -1430,11 +1401,7 @@ __device__ static int cz_chunk_copy(CzExecCtx& x, const CzLit& lit, const CzPlan
         const int near = ml > 0 && !far;
         const int far_plain = far && off >= ml, far_period = far && off < ml;
         const uint8_t* ls = lit.p + lit_start;
-#ifdef CZ_EXP_NEARSRC   /* diagnostic only (wrong output): far match sources read next to the chunk instead of anywhere in the window */
-        const uint8_t* ms = x.produced >= 4096 ? cout - 8 - ((drel * 7u + off) & 1023u) : cout + (drel - (uint64_t)off);
-#else
         const uint8_t* ms = cout + (drel - (uint64_t)off);
-#endif
         /* first group of every lane: all loads, then all LDS writes; sized by the longest run of the chunk */
         const int lit_wide = !__ballot(ll > 0 && !lit.rle && (uint64_t)lit_start + 8 > lit.len);   /* 8-byte literal loads stay inside the buffer */
         const unsigned long long big = __ballot(ll > 4 || ml > 8), mid = __ballot(ll > 2 || ml > 4);
@@ -1453,11 +1420,7 @@ __device__ static int cz_chunk_copy(CzExecCtx& x, const CzLit& lit, const CzPlan
         CZ_PROF_ACC(CZ_P_LITCOPY);
         /* matches that read this chunk's output: rounds.  W = destination of the first undone match;
            a match may go once its source range (clipped to its own destination) lies below W. */
-#ifdef CZ_EXP_NOROUNDS   /* diagnostic only (wrong output): ... without the dependency rounds */
-        int done = 1;
-#else
         int done = !near;
-#endif
         const int32_t send = srel + (int32_t)span;                      /* <= drel */
         for (;;) {
             const unsigned long long pend = __ballot(!done);
@@ -1466,8 +1429,8 @@ __device__ static int cz_chunk_copy(CzExecCtx& x, const CzLit& lit, const CzPlan
             const int32_t W = (int32_t)cz_readlane(drel, cz_unii(f));
             const int ready = !done && send <= W;
             if (ready) {
-#if defined(CZ_EXEC_ONLY) && !defined(CZ_EXP_L2L_OFF)   /* (cz_decode_frames_kernel keeps the byte loop: with cz_lane_l2l in it this compiler ended
-                                                           its build with "Illegal instruction detected: V_CMP_NE_U32_e32 0, $src_shared_base") */
+#if defined(CZ_EXEC_ONLY)   /* (cz_decode_frames_kernel keeps the byte loop: with cz_lane_l2l in it this compiler ended
+                               its build with "Illegal instruction detected: V_CMP_NE_U32_e32 0, $src_shared_base") */
                 if (srel >= 0) cz_lane_l2l(ob, drel, off, ml);          /* the source lies inside the chunk buffer: 8 bytes a step */
                 else
 #endif
@@ -1485,19 +1448,10 @@ __device__ static int cz_chunk_copy(CzExecCtx& x, const CzLit& lit, const CzPlan
         }
         /* write the assembled chunk: 16 bytes per lane per pass (the global address need not be aligned).
            Later loads of these bytes by this wave are ordered behind the stores by the memory pipeline. */
-#ifndef CZ_EXP_NOSTORE   /* diagnostic only (wrong output): ... without the stores of the assembled chunk */
-#ifdef CZ_EXP_STORE4
-        for (uint32_t i = 4u * (uint32_t)LANE; i < sum_tot; i += 256) {
-            if (i + 4 <= sum_tot) { uint32_t w = *(const uint32_t*)(ob + i); __builtin_memcpy(cout + i, &w, 4); }
-            else for (uint32_t j = i; j < sum_tot; j++) cout[j] = ob[j];
-        }
-#else
         for (uint32_t i = 16u * (uint32_t)LANE; i < sum_tot; i += 1024) {
             if (i + 16 <= sum_tot) { const uint4 w = *(const uint4*)(ob + i); __builtin_memcpy(cout + i, &w, 16); }
             else for (uint32_t j = i; j < sum_tot; j++) cout[j] = ob[j];
         }
-#endif
-#endif
         cz_wave_sync();
         CZ_PROF_ACC(CZ_P_MATCH);
         x.produced += sum_tot; x.lit_used += sum_ll;
@@ -1961,11 +1915,7 @@ __device__ static __attribute__((noinline)) int cz_sequences_rec_general(CzExecC
         const uint32_t cnt = nseq - at < 64 ? nseq - at : 64;
         uint32_t ll = 0, ml = 0, ov = 4;
         if ((uint32_t)LANE < cnt) ov = cz_rec_values(r, bits, ll, ml);
-#ifdef CZ_EXP_NOHIST   /* diagnostic only (wrong output): instruction count of the chunk loop without the repeat-offset scan */
-        const uint32_t actual = ov > 3 ? ov - 3 : h0 + ov;
-#else
         const uint32_t actual = cz_history(cnt, ll, ov, h0, h1, h2);
-#endif
         return cz_chunk_plan(x, produced, lit_used, lit, cnt, ll, ml, actual);
     };
     /* Records are loaded three chunks ahead; each chunk is planned (codes -> values, repeat offsets,
@@ -1977,11 +1927,7 @@ __device__ static __attribute__((noinline)) int cz_sequences_rec_general(CzExecC
         r1 = r2; r2 = r3; r3 = load_rec(done + 192);
         if (cur.err > 0) return cur.err;
         CZ_PROF_ACC(CZ_P_EXTRACT);
-#ifdef CZ_EXP_NOCOPY   /* diagnostic only (wrong output): ... without the copy stage */
-        x.produced += cur.sum_tot; x.lit_used += cur.sum_ll; exec_err = 0;
-#else
         exec_err = cz_chunk_copy(x, lit, cur);
-#endif
         CZ_PROF_T0();
         if (exec_err) return exec_err;
         cz_wave_sync();
@@ -2038,11 +1984,7 @@ __device__ static __attribute__((noinline)) int cz_sequences_rec_fast(CzExecCtx&
     uint32_t P = cz_uni((uint32_t)xref.produced), lit_used = cz_uni(xref.lit_used);
     uint32_t h0 = cz_uni(sh.hist[0]), h1 = cz_uni(sh.hist[1]), h2 = cz_uni(sh.hist[2]);
     uint8_t* const ob = sh.a.t4.obuf;
-#if defined(CZ_EXP_NT_REC) && defined(__HIP_DEVICE_COMPILE__)
-    auto load_rec = [&](uint32_t first) -> uint64_t { const uint32_t i = first + (uint32_t)LANE; return __builtin_nontemporal_load(&rec[i < nseq ? i : nseq - 1]); };   /* (diagnostic: records are read once — keep them out of the caches' way) */
-#else
     auto load_rec = [&](uint32_t first) -> uint64_t { const uint32_t i = first + (uint32_t)LANE; return rec[i < nseq ? i : nseq - 1]; };   /* coalesced 8-byte loads */
-#endif
     uint32_t done = cz_uni(first_);
     uint64_t r1 = load_rec(done), r2 = load_rec(done + 64), r3 = load_rec(done + 128);
     for (; done < nseq; done += 64) {
@@ -2136,15 +2078,12 @@ __device__ static __attribute__((noinline)) int cz_sequences_rec_fast(CzExecCtx&
    the fast loop cannot take goes through the general loop on its own; after CZ_FAST_MISSES of those the general loop takes the
    rest of the frame.  (Handing blocks back to the fast loop — after every chunk, after stretches of 2..8 chunks, or after 4..16
    chunks in a row that it would have taken — was measured on the corpus-like mix: every variant lost, 8.0-12.8 ms against 7.6.) */
-#ifndef CZ_FAST_MISSES
 #define CZ_FAST_MISSES 6u
-#endif
 __device__ static int cz_sequences_rec(CzExecCtx& x, const CzLit lit, cz_gcptr64 maps, cz_gcptr64 rec, uint32_t nseq, uint32_t mapflags, cz_gcptr bits) {
     CZ_PROF_DECL; CZ_PROF_T0();
     /* the fast loop wants every position of the frame in 32 bits, no drained bytes and no dictionary content (then offset <=
        position is the whole reach test of decode_buffer.cairo:62-93) */
     uint32_t first = 0;
-#ifndef CZ_EXP_NOFAST
     if (cz_uni64(x.cap) < 0xC0000000ull && cz_uni64(x.drained) == 0 && (sh.dict_len[0] | sh.dict_len[1]) == 0 && cz_uni(sh.rec_misses) <= CZ_FAST_MISSES) {
         uint32_t flags = mapflags;
         for (;;) {
@@ -2161,9 +2100,7 @@ __device__ static int cz_sequences_rec(CzExecCtx& x, const CzLit lit, cz_gcptr64
             cz_wave_sync();
             first = end;
         }
-    } else
-#endif
-    cz_rec_load_maps(maps, mapflags);
+    } else cz_rec_load_maps(maps, mapflags);
     CZ_PROF_ACC(CZ_P_RING);
     const int e = cz_sequences_rec_general(x, lit, rec, nseq, bits, first, nseq);
     if (e) return e;
@@ -2583,7 +2520,7 @@ extern "C" __global__ void __launch_bounds__(CZ_WG_THREADS, CZ_EXEC_WAVES) CZ_EX
        CZ_DEBUG_EXEC_LEAVE (test knob): every wave takes the leave branch at once, as if it were on an even CU nobody met. */
     if (wx_on) {
         uint32_t leave = (a.debug_flags & CZ_DEBUG_EXEC_LEAVE) != 0u;
-#if !defined(CZ_EXP_NO_SIDE) && !defined(CZ_EMU)                       /* (the emulator runs the kernels one after the other: no CUs to share) */
+#if !defined(CZ_EMU)                                                   /* (the emulator runs the kernels one after the other: no CUs to share) */
         if (!leave && cz_uni(a.scan_ctl[206]) != 0u && ::cz_cu_side() == 1u) {
             uint32_t polls = 0;
             while (*(volatile uint32_t*)&a.scan_ctl[213] < a.wx_cus && polls < 8u) { __builtin_amdgcn_s_sleep(127); polls++; }

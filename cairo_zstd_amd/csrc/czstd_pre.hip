@@ -27,9 +27,7 @@
  * cz_tile_kernel: Raw / RLE runs whose place is known from the headers (block_decoder.cairo:95-122): one workgroup of 256
  * threads per run (at most 128 KiB), taken from a shared counter, 16 bytes per thread and step, eight loads in flight per thread.
  */
-#ifndef CZH_WAVES
 #define CZH_WAVES 2                       /* waves per workgroup: wave w decodes streams w, w + CZH_WAVES, ... (two workgroups fit next to cz_chain_kernel's 135 KB of LDS) */
-#endif
 #define CZH_THREADS (64 * CZH_WAVES)
 #define CZH_TILE 1024u                    /* bytes of bitstream per tile: 16 per lane */
 #define CZH_STG 2048u                     /* symbols staged per flush (one tile of 5-bit codes yields about 1 640) */
@@ -282,7 +280,7 @@ __device__ static inline void czh_hand_back(const cz_batch_args& a, uint32_t f) 
     cz_list_fallback(a, f);
 }
 
-extern "C" __global__ void __launch_bounds__(CZH_THREADS, CZH_WAVES == 2 ? 6 : 8) cz_huf_kernel(cz_batch_args a) {
+extern "C" __global__ void __launch_bounds__(CZH_THREADS, 6) cz_huf_kernel(cz_batch_args a) {
     const uint32_t wave = threadIdx.x >> 6;
     uint32_t nseg = 0; for (int c = 0; c < 20; c++) nseg += a.scan_ctl[136 + c];
     if (nseg > a.lit_seg_capacity) nseg = a.lit_seg_capacity;

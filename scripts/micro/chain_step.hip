@@ -1,4 +1,4 @@
-// Diagnostic microbenchmark: cost of the pieces of the chain step (czstd_chain.hip, czc_group_asm) on ONE wave
+// Diagnostic microbenchmark: cost of the pieces of the chain step (czstd_chain.hip, czc_group_asm2) on ONE wave
 // per SIMD.  Variants remove / replace pieces of the step; the chain data is synthetic (a table whose
 // entries keep every state in range), so only time is meaningful.
 //   hipcc --offload-arch=gfx950 -O3 chain_step.hip -o chain_step && ./chain_step
@@ -7,7 +7,7 @@
 #include <cstdint>
 #define CHECK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 
-// pieces of the current step (czstd_chain.hip, CZC_ASM_HEAD / CZC_ASM_TAIL)
+// pieces of the round-4 step (retired from czstd_chain.hip; CZC_ASMW_HEAD / CZC_ASMW_TAIL of the wide group still pick the field this way)
 #define H1 "s_waitcnt lgkmcnt(3)\n" "v_ffbh_u32 v100, %[E]\n" "v_and_or_b32 v101, %[E], %[XM], %[K64]\n" "v_lshrrev_b32 v103, 22, %[E]\n" "v_sub_u32 v102, v101, v100\n"
 #define NOP1 "s_nop 1\n"
 #define NOP0 "s_nop 0\n"

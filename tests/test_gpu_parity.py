@@ -1010,7 +1010,7 @@ def test_r3_vectors_vs_manifest(cz, prepass):
         c.close()
 
 def test_chain_kernel_asm_group_and_cpp_step_leave_the_same_records(cz):
-    """cz_chain_kernel's hand-scheduled inline-asm group (czc_group_asm, and its wide variant) against the plain C++ step
+    """cz_chain_kernel's hand-scheduled inline-asm group (czc_group_asm2, and its wide variant) against the plain C++ step
     (czc_step), which the CPU emulator runs: the same blocks through both, and the chain arenas — headers, state -> code maps and
     the 8-byte record of every sequence (sequence_section_decoder.cairo:223-286) — compared word for word."""
     from cairo_zstd_amd import synth
