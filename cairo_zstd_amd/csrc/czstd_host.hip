@@ -22,6 +22,7 @@
 #include <queue>
 #include <system_error>
 #include <thread>
+#include <tuple>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -36,6 +37,7 @@
 #include "czstd_encsplit.hip" /* cz_compress_plan_kernel, cz_compress_segments_kernel (CZ_COMPRESS_SPLIT) */
 #include "czstd_encfse.hip"   /* cz_compress_frames_fse_kernel, cz_compress_segments_fse_kernel (CZ_COMPRESS_FSE_TABLES) */
 #include "czstd_encfast.hip"  /* cz_compress_frames_fast_kernel (CZ_COMPRESS_FAST) */
+#include "czstd_encfastsplit.hip" /* cz_compress_fast_plan_kernel, cz_compress_groups_fast_kernel (CZ_COMPRESS_FAST_SPLIT) */
 #include "czstd_encrec.hip"   /* cz_compress_records_kernel, cz_compress_records_dict_kernel (CZ_COMPRESS_RECORDS) */
 #include "czstd_train.hip"    /* cz_train_*_kernel (cz_dictionary_train_*) */
 /* the same kernel source once more, without its decoders: cz_execute_frames_kernel (czstd_kernels.hip, CZ_EXEC_ONLY) */
@@ -74,7 +76,7 @@ struct cz_dictionary {
 /* One scratch of the compress kernels: `slots` workgroups' worth, and per kernel that runs on it (the second: the kernel with
    dictionaries) as many workgroups as the device holds at once, asked of the occupancy API on first use. */
 struct cz_enc_level { uint8_t* scratch = nullptr; int slots = 0; int grid[2] = {0, 0}; };
-enum { CZ_ENC_PLAIN, CZ_ENC_SPLIT, CZ_ENC_FSE, CZ_ENC_SPLIT_FSE, CZ_ENC_FAST, CZ_ENC_RECORDS, CZ_ENC_LEVELS };
+enum { CZ_ENC_PLAIN, CZ_ENC_SPLIT, CZ_ENC_FSE, CZ_ENC_SPLIT_FSE, CZ_ENC_FAST, CZ_ENC_RECORDS, CZ_ENC_FAST_SPLIT, CZ_ENC_LEVELS };
 struct cz_context {
     int device = 0;
     hipStream_t stream = nullptr; bool own_stream = false;
@@ -100,7 +102,8 @@ struct cz_context {
     /* batched compression (cz_compress_batch_*): one cz_enc_level per scratch, allocated by the first call that takes the level;
        the 32-bit work counter every level but split claims its work from */
     cz_enc_level enc[CZ_ENC_LEVELS]; uint32_t* enc_counter = nullptr;
-    /* CZ_COMPRESS_SPLIT: unit_base (n + 1) and the per-frame state (2 n) in one allocation sized from n; the unit counter */
+    /* CZ_COMPRESS_SPLIT, CZ_COMPRESS_FAST_SPLIT: unit_base (n + 1) and the per-frame state (2 n or 3 n words) in one allocation sized
+       from n; the unit counter */
     unsigned long long* encs_plan = nullptr; size_t encs_frames = 0; unsigned long long* encs_counter = nullptr;
     cze_dict_entry* enc_dicts = nullptr; uint32_t enc_dict_count = 0;   /* cz_context_set_compress_dictionaries */
     float train_ms[4] = {0.f, 0.f, 0.f, 0.f};                           /* cz_dictionary_train_last_ms */
@@ -958,11 +961,12 @@ static int cz_enc_counter(cz_context* c) {
     CZ_HIP(c, hipMemsetAsync(c->enc_counter, 0, 4, c->stream));
     return CZ_OK;
 }
-/* CZ_COMPRESS_SPLIT: the plan arrays for n frames and the unit counter, kept and grown like a scratch; the counter cleared */
+/* CZ_COMPRESS_SPLIT, CZ_COMPRESS_FAST_SPLIT: the plan arrays for n frames (unit_base, then up to three words of state per frame)
+   and the unit counter, kept and grown like a scratch; the counter cleared */
 static int cz_enc_split_plan(cz_context* c, size_t n) {
     if (c->encs_frames < n) {
         if (c->encs_plan) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->encs_plan); c->encs_plan = nullptr; c->encs_frames = 0; }
-        CZ_HIP(c, hipMalloc((void**)&c->encs_plan, (3 * n + 1) * sizeof(unsigned long long)));
+        CZ_HIP(c, hipMalloc((void**)&c->encs_plan, (4 * n + 1) * sizeof(unsigned long long)));
         c->encs_frames = n;
     }
     if (!c->encs_counter) CZ_HIP(c, hipMalloc((void**)&c->encs_counter, 64));
@@ -980,8 +984,9 @@ static cz_enc_args cz_enc_fill(const cz_enc_batch& b, uint32_t* work_counter, ui
 /* The launch of every compress level, on the context stream: persistent workgroups of `kernel`, as many as fit on the device
    but no more than `cap` (there is no work for more), each with `stride` bytes of the level's scratch; they claim their work
    from a counter.  `which` picks the kernel's grid in the level, `extra` is what the kernel takes after its cz_enc_args (the
-   dictionaries).  The segment kernels (CZ_COMPRESS_SPLIT) take a cz_encsplit_args instead: the plan kernel runs first (units per
-   frame, scanned; the host knows n only) and the units come from a counter of their own. */
+   dictionaries).  The kernels that work on units (CZ_COMPRESS_SPLIT, CZ_COMPRESS_FAST_SPLIT) take a cz_encsplit_args instead and
+   `extra` is their level's plan kernel: it runs first (units per frame, scanned; the host knows n only) and the units come from a
+   counter of their own. */
 template <typename K, typename... X>
 static int cz_enc_launch(cz_context* c, const cz_enc_batch& b, cz_enc_level& l, int which, size_t stride, size_t cap, K kernel, X... extra) {
     constexpr bool split = std::is_same<K, void (*)(cz_encsplit_args)>::value;
@@ -993,7 +998,7 @@ static int cz_enc_launch(cz_context* c, const cz_enc_batch& b, cz_enc_level& l, 
     if constexpr (split) {
         cz_encsplit_args sa; memset(&sa, 0, sizeof sa);
         sa.a = a; sa.unit_base = c->encs_plan; sa.fstate = c->encs_plan + b.n + 1; sa.counter = c->encs_counter;
-        hipLaunchKernelGGL(cz_compress_plan_kernel, dim3(1), dim3(CZE_THREADS), 0, c->stream, b.in_len, (uint32_t)b.n, b.flags, sa.unit_base, sa.fstate);
+        hipLaunchKernelGGL(std::get<0>(std::make_tuple(extra...)), dim3(1), dim3(CZE_THREADS), 0, c->stream, b.in_len, (uint32_t)b.n, b.flags, sa.unit_base, sa.fstate);
         CZ_HIP(c, hipGetLastError());
         hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(CZE_THREADS), 0, c->stream, sa);
     } else {
@@ -1004,8 +1009,10 @@ static int cz_enc_launch(cz_context* c, const cz_enc_batch& b, cz_enc_level& l, 
     return CZ_OK;
 }
 
-/* the flags cz_compress_batch_device / _host take: CZ_COMPRESS_FAST and CZ_COMPRESS_RECORDS each go with the checksum alone */
+/* the flags cz_compress_batch_device / _host take: CZ_COMPRESS_FAST, CZ_COMPRESS_RECORDS and CZ_COMPRESS_FAST_SPLIT each go with the
+   checksum alone */
 static bool cz_compress_flags_ok(uint32_t flags) {
+    if (flags & CZ_COMPRESS_FAST_SPLIT) return !(flags & ~(CZ_COMPRESS_FAST_SPLIT | CZ_COMPRESS_CHECKSUM));
     if (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_SPLIT | CZ_COMPRESS_FSE_TABLES | CZ_COMPRESS_FAST | CZ_COMPRESS_RECORDS)) return false;
     if ((flags & CZ_COMPRESS_RECORDS) && (flags & (CZ_COMPRESS_SPLIT | CZ_COMPRESS_FSE_TABLES | CZ_COMPRESS_FAST))) return false;
     return !(flags & CZ_COMPRESS_FAST) || !(flags & (CZ_COMPRESS_SPLIT | CZ_COMPRESS_FSE_TABLES));
@@ -1026,8 +1033,11 @@ CZ_EXPORT int cz_compress_batch_device(cz_context* c, const void* d_in_base, con
     cz_enc_level* const l = c->enc;                                     /* the host picks the kernel; each level has its own scratch */
     const size_t all = ~(size_t)0, waves = (n + CZE_WAVES - 1) / CZE_WAVES;   /* split: units, not frames; records: a wave per record */
     if ((flags & CZ_COMPRESS_SPLIT) && (flags & CZ_COMPRESS_FSE_TABLES))
-        return cz_enc_launch(c, b, l[CZ_ENC_SPLIT_FSE], 0, CZE_FSE_SPLIT_SCRATCH_BYTES, all, cz_compress_segments_fse_kernel);
-    if (flags & CZ_COMPRESS_SPLIT) return cz_enc_launch(c, b, l[CZ_ENC_SPLIT], 0, CZE_SPLIT_SCRATCH_BYTES, all, cz_compress_segments_kernel);
+        return cz_enc_launch(c, b, l[CZ_ENC_SPLIT_FSE], 0, CZE_FSE_SPLIT_SCRATCH_BYTES, all, cz_compress_segments_fse_kernel, cz_compress_plan_kernel);
+    if (flags & CZ_COMPRESS_SPLIT)
+        return cz_enc_launch(c, b, l[CZ_ENC_SPLIT], 0, CZE_SPLIT_SCRATCH_BYTES, all, cz_compress_segments_kernel, cz_compress_plan_kernel);
+    if (flags & CZ_COMPRESS_FAST_SPLIT)
+        return cz_enc_launch(c, b, l[CZ_ENC_FAST_SPLIT], 0, CZE_FAST_SCRATCH_BYTES, all, cz_compress_groups_fast_kernel, cz_compress_fast_plan_kernel);
     if (flags & CZ_COMPRESS_FSE_TABLES) return cz_enc_launch(c, b, l[CZ_ENC_FSE], 0, CZE_FSE_SCRATCH_BYTES, n, cz_compress_frames_fse_kernel);
     if (flags & CZ_COMPRESS_FAST) return cz_enc_launch(c, b, l[CZ_ENC_FAST], 0, CZE_FAST_SCRATCH_BYTES, n, cz_compress_frames_fast_kernel);
     if (flags & CZ_COMPRESS_RECORDS) return cz_enc_launch(c, b, l[CZ_ENC_RECORDS], 0, CZE_RECORDS_SCRATCH_BYTES, waves, cz_compress_records_kernel);

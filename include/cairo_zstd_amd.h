@@ -505,6 +505,21 @@ uint64_t cz_compress_split_segment(void);   /* the segment size S in bytes */
  */
 #define CZ_COMPRESS_RECORDS 64u
 uint64_t cz_compress_record_max(void);   /* 32768: the largest input CZ_COMPRESS_RECORDS takes */
+/*
+ * CZ_COMPRESS_FAST_SPLIT (cz_compress_batch_device / _host only, alone or with CZ_COMPRESS_CHECKSUM): the fast
+ * level for few, large buffers.  The 128 KiB groups of one input are compressed by different workgroups at the same time, so one
+ * buffer occupies the whole device.  For every input the frame is byte for byte the CZ_COMPRESS_FAST frame of the same input and
+ * checksum flag, and status, blocks, bytes_read, bytes_written and checksum are equal too, for every out_cap: that includes
+ * CZ_E_OUTPUT_TOO_SMALL where the header does not fit, where a group does not fit (the frame ends at that group boundary) and where
+ * the 4 checksum bytes do not fit, and CZ_E_INVALID_ARG for an input of 0xFFF00000 bytes or more.  Only `flags` differs: it carries
+ * 128 where the fast frame carries 32.  Nothing past bytes_written is touched.  The bytes depend on the input and the flags alone,
+ * never on the batch, the grid or timing.  CZ_E_WAIT_EXPIRED is possible, as described for CZ_COMPRESS_SPLIT.  An input of at most
+ * one group is one unit of work, as at the fast level: for batches of very many buffers of 128 KiB or less CZ_COMPRESS_FAST does
+ * the same work without the plan launch and the search per unit.
+ * The value is 128, a bit of its own (CZ_COMPRESS_FAST | CZ_COMPRESS_SPLIT stays CZ_E_INVALID_ARG; 8 stays an unknown bit).
+ * CZ_E_INVALID_ARG together with any other flag but the checksum and in cz_compress_batch_dict_*.
+ */
+#define CZ_COMPRESS_FAST_SPLIT 128u
 /* One per buffer, written by the device. */
 typedef struct cz_compress_result {
     int32_t  status;            /* CZ_OK | CZ_E_OUTPUT_TOO_SMALL | CZ_E_INVALID_ARG (an input of 4 GiB - 1 MiB or more) | CZ_E_WAIT_EXPIRED */
@@ -518,7 +533,8 @@ typedef struct cz_compress_result {
  * (results too); asynchronous on the context stream; no alignment required.  A frame that fails leaves its neighbours and
  * every byte of its own region past bytes_written untouched.  out_cap[i] = cz_compress_bound(in_len[i]) always suffices.
  * flags: CZ_COMPRESS_CHECKSUM, CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES, CZ_COMPRESS_FAST (not with the two before it),
- * CZ_COMPRESS_RECORDS (not with the three before it); any other bit is CZ_E_INVALID_ARG. */
+ * CZ_COMPRESS_RECORDS (not with the three before it), CZ_COMPRESS_FAST_SPLIT (with the checksum only); any other bit is
+ * CZ_E_INVALID_ARG. */
 int cz_compress_batch_device(cz_context* ctx, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                              void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                              cz_compress_result* d_results);
