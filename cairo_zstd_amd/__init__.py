@@ -12,6 +12,8 @@ Python here is a thin mirror over the C ABI (include/cairo_zstd_amd.h, libcairo_
   * compress_batch_host_dict / Context.compress_batch_dict_device : the same with dictionaries (Context.set_compress_dictionaries;
     records=True: the records level with dictionaries)
   * train_dictionary / Context.train_dictionary_device : a zstd dictionary made from samples on the device
+  * Context.seekable_pack_device / Context.seekable_open_device / decode_seekable : a batch of frames as one seekable stream (the
+    frames back to back and a seek table), packed and opened on the device; pack_seekable / open_seekable: the same on the CPU
 All decoding and compression runs in the HIP kernels; nothing here decodes or compresses on the CPU.
 """
 from __future__ import annotations
@@ -22,7 +24,7 @@ import weakref
 import numpy as np
 
 from . import status
-from ._lib import (COMPRESS_CHECKSUM, COMPRESS_FAST, COMPRESS_FAST_SPLIT, COMPRESS_RECORDS, COMPRESS_FSE_TABLES, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, COMPRESS_SPLIT, TRAIN_MIN_CAPACITY, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
+from ._lib import (COMPRESS_CHECKSUM, COMPRESS_FAST, COMPRESS_FAST_SPLIT, COMPRESS_RECORDS, COMPRESS_FSE_TABLES, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, COMPRESS_SPLIT, SEEKABLE_CHECKSUMS, SEEKABLE_INFO_DTYPE, TRAIN_MIN_CAPACITY, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
                    BlockHeader, FrameHeader, build, lib)
 
 DEBUG_CHAIN_CPP_STEP, DEBUG_NO_HUF1, DEBUG_WX_POISON, DEBUG_EXEC_FIRST, DEBUG_EXEC_LEAVE = 1, 2, 4, 8, 16     # cz_context_set_debug_flags
@@ -32,7 +34,8 @@ __all__ = ["Context", "FrameDecoder", "BlockDecodingStrategy", "decode_batch_hos
            "read_block_header", "graph_replay_available", "RESULT_DTYPE", "RESULT_FINISHED", "RESULT_HAS_CHECKSUM", "RESULT_CHECKSUM_COMPUTED",
            "RESULT_CHECKSUM_MATCH", "status", "CzError", "build", "lib", "compress_bound", "compress_batch_host", "compress",
            "COMPRESS_CHECKSUM", "COMPRESS_RESULT_DTYPE", "compress_batch_host_dict", "COMPRESS_NO_DICT", "COMPRESS_NO_DICT_ID",
-           "COMPRESS_SPLIT", "compress_split_segment", "COMPRESS_FSE_TABLES", "COMPRESS_FAST", "COMPRESS_FAST_SPLIT", "COMPRESS_RECORDS", "compress_record_max", "train_dictionary", "TRAIN_MIN_CAPACITY"]
+           "COMPRESS_SPLIT", "compress_split_segment", "COMPRESS_FSE_TABLES", "COMPRESS_FAST", "COMPRESS_FAST_SPLIT", "COMPRESS_RECORDS", "compress_record_max", "train_dictionary", "TRAIN_MIN_CAPACITY",
+           "SEEKABLE_CHECKSUMS", "SEEKABLE_INFO_DTYPE", "seekable_bound", "pack_seekable", "open_seekable", "decode_seekable"]
 
 
 def _as_u8(b) -> np.ndarray:
@@ -380,6 +383,30 @@ class Context:
             raise CzError(st, f"cz_dictionary_train_host (hip error {lib().cz_context_last_hip_error(self._h)})")
         return out, int(got.value)
 
+    def seekable_pack_device(self, frames_base: int, frame_off: int, results: int, n: int, stream: int, stream_cap: int, info: int,
+                             checksums: bool = False):
+        """cz_seekable_pack_device: the n frames a compress_batch_*device call left at frames_base + frame_off[i] (their lengths and
+        sizes in `results`) back to back into `stream`, followed by the seek table.  All arguments are raw DEVICE pointers, `info`
+        (one SEEKABLE_INFO_DTYPE record, which carries the status of everything decided on the device) included.  Asynchronous on
+        the context's stream and never synchronises: directly behind the compress launch it needs no host step in between."""
+        st = lib().cz_seekable_pack_device(self._h, frames_base or None, frame_off or None, results or None, n, stream, stream_cap,
+                                           SEEKABLE_CHECKSUMS if checksums else 0, info)
+        if st:
+            raise CzError(st, f"cz_seekable_pack_device (hip error {lib().cz_context_last_hip_error(self._h)})")
+
+    def seekable_open_device(self, stream: int, stream_len: int, first: int = 0, count: int | None = None, out_align: int = 1,
+                             in_off: int = 0, in_len: int = 0, out_off: int = 0, out_cap: int = 0, checksum: int = 0):
+        """cz_seekable_open_device: validates the seek table of the stream at the DEVICE pointer `stream` and writes the arrays of
+        decode_batch_device for frames [first, first + count) (count None: up to the end) to the DEVICE pointers given (0: not
+        wanted; all 0: the sizing call).  Synchronises.  Returns the SEEKABLE_INFO_DTYPE record: status (CZ_OK, CZ_E_SEEK_TABLE with
+        its reason, CZ_E_INVALID_ARG), the table's sums, and in `detail` the output bytes the range needs."""
+        info = np.zeros(1, dtype=SEEKABLE_INFO_DTYPE)
+        st = lib().cz_seekable_open_device(self._h, stream or None, stream_len, first, 0xFFFFFFFFFFFFFFFF if count is None else count, out_align,
+                                           in_off or None, in_len or None, out_off or None, out_cap or None, checksum or None, info.ctypes.data)
+        if st == status.CZ_E_HIP:
+            raise CzError(st, f"cz_seekable_open_device (hip error {lib().cz_context_last_hip_error(self._h)})")
+        return info[0]
+
     def last_train_ms(self):
         """cz_dictionary_train_last_ms: device milliseconds of the last training's steps (frequencies, epochs, statistics, tables)."""
         ms = (C.c_float * 4)()
@@ -399,6 +426,89 @@ def train_dictionary(samples, capacity: int, ctx: Context, dict_id: int = 0, seg
     base = np.frombuffer(b"".join(bytes(b) for b in samples) + b"\0" * 16, dtype=np.uint8)
     out, n = ctx.train_dictionary_host(base, off, lens, capacity, dict_id=dict_id, segment_len=segment_len)
     return out[:n].tobytes()
+
+
+def seekable_bound(frame_bytes: int, n: int, checksums: bool = False) -> int:
+    """cz_seekable_bound: the bytes of the seekable stream of n frames of frame_bytes bytes together."""
+    return int(lib().cz_seekable_bound(frame_bytes, n, SEEKABLE_CHECKSUMS if checksums else 0))
+
+
+def pack_seekable(frames, content_sizes, checksums=None) -> bytes:
+    """cz_seekable_pack_host (on the CPU, no device): the frames back to back and the seek table with their lengths, content_sizes
+    and, when given, checksums (the low 32 bits of XXH64 of each frame's content)."""
+    n = len(frames)
+    res = np.zeros(max(n, 1), dtype=COMPRESS_RESULT_DTYPE)
+    lens = np.array([len(f) for f in frames], dtype=np.uint64)
+    res["bytes_written"][:n] = lens
+    res["bytes_read"][:n] = np.asarray(content_sizes, dtype=np.uint64)
+    if checksums is not None:
+        res["checksum"][:n] = np.asarray(checksums, dtype=np.uint32)
+        res["flags"][:n] = COMPRESS_CHECKSUM
+    off = np.zeros(max(n, 1), dtype=np.uint64)
+    off[1:n] = np.cumsum(lens[:-1])
+    base = np.frombuffer(b"".join(bytes(f) for f in frames) + b"\0", dtype=np.uint8)
+    cap = seekable_bound(int(lens.sum()), n, checksums is not None)
+    out = np.zeros(cap, dtype=np.uint8)
+    info = np.zeros(1, dtype=SEEKABLE_INFO_DTYPE)
+    st = lib().cz_seekable_pack_host(base.ctypes.data, off.ctypes.data, res.ctypes.data, n, out.ctypes.data, cap,
+                                     SEEKABLE_CHECKSUMS if checksums is not None else 0, info.ctypes.data)
+    if st:
+        raise CzError(st, f"cz_seekable_pack_host (frame {int(info[0]['detail'])})")
+    return out[:int(info[0]["stream_bytes"])].tobytes()
+
+
+def open_seekable(stream, first: int = 0, count: int | None = None, out_align: int = 1):
+    """cz_seekable_open_host (on the CPU, no device): (info, in_off, in_len, out_off, out_cap, checksums) of frames
+    [first, first + count) of a seekable stream (count None: up to the end), the arrays as decode_batch_* take them.  `info` is the
+    SEEKABLE_INFO_DTYPE record; when its status is not CZ_OK (CZ_E_SEEK_TABLE with the reason, CZ_E_INVALID_ARG) the arrays are empty."""
+    a = _as_u8(stream)
+    info = np.zeros(1, dtype=SEEKABLE_INFO_DTYPE)
+    none = 0xFFFFFFFFFFFFFFFF
+    st = lib().cz_seekable_open_host(a.ctypes.data if a.size else None, a.size, first, none if count is None else count, out_align,
+                                     None, None, None, None, None, info.ctypes.data)
+    k = 0
+    if not st:
+        k = int(info[0]["frames"]) - first if count is None else count
+    arr = [np.zeros(k, dtype=np.uint64) for _ in range(4)] + [np.zeros(k, dtype=np.uint32)]
+    if k:
+        lib().cz_seekable_open_host(a.ctypes.data, a.size, first, k, out_align, *[x.ctypes.data for x in arr], info.ctypes.data)
+    return (info[0], *arr)
+
+
+def decode_seekable(stream, ctx: Context, first: int = 0, count: int | None = None):
+    """Frames [first, first + count) of a seekable stream (count None: up to the end), decoded: a list of bytes.  The stream is
+    staged in HBM, its table opened there (cz_seekable_open_device) and the range decoded by ONE decode_batch_device; nothing but
+    the stream goes up and nothing but the decoded bytes and the result records come down.  Raises CzError on a malformed table,
+    a range outside it, or a frame that fails."""
+    import torch
+    a = _as_u8(stream)
+    dev = torch.device(f"cuda:{ctx.device}")
+    d_stream = torch.zeros(a.size + 64, dtype=torch.uint8, device=dev)
+    d_stream[:a.size] = torch.from_numpy(a.copy())
+    torch.cuda.synchronize(dev)
+    info = ctx.seekable_open_device(d_stream.data_ptr(), a.size, first, count, 256)
+    if int(info["status"]):
+        raise CzError(int(info["status"]), f"cz_seekable_open_device (reason {int(info['reason'])})")
+    k = int(info["frames"]) - first if count is None else count
+    if k == 0:
+        return []
+    desc = torch.zeros((4, k), dtype=torch.int64, device=dev)
+    d_out = torch.zeros(int(info["detail"]) + 256, dtype=torch.uint8, device=dev)
+    d_res = torch.zeros(k * RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    info = ctx.seekable_open_device(d_stream.data_ptr(), a.size, first, k, 256, desc[0].data_ptr(), desc[1].data_ptr(), desc[2].data_ptr(),
+                                    desc[3].data_ptr())
+    if int(info["status"]):
+        raise CzError(int(info["status"]), "cz_seekable_open_device")
+    ctx.decode_batch_device(d_stream.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), k, d_out.data_ptr(), desc[2].data_ptr(),
+                            desc[3].data_ptr(), d_res.data_ptr())
+    ctx.synchronize()
+    res = d_res.cpu().numpy().view(RESULT_DTYPE)
+    out, off = d_out.cpu().numpy(), desc[2].cpu().numpy()
+    for i in range(k):
+        if int(res[i]["status"]):
+            raise CzError(int(res[i]["status"]), f"frame {first + i}")
+    return [out[int(off[i]): int(off[i]) + int(res[i]["bytes_produced"])].tobytes() for i in range(k)]
 
 
 def _compress_flags(checksum, split, fse_tables, fast=False, records=False, fast_split=False) -> int:

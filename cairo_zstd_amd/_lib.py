@@ -31,6 +31,11 @@ COMPRESS_FAST = 32                      # the fast level: 32 KiB blocks that sta
 COMPRESS_RECORDS = 64                   # the records level: one wave per record of at most compress_record_max(), with or without dictionaries
 COMPRESS_FAST_SPLIT = 128              # the fast level with the 128 KiB groups of one buffer on many workgroups: the COMPRESS_FAST frame, byte for byte (with the checksum only)
 COMPRESS_NO_DICT = 0xFFFFFFFF           # dict_index entry: no dictionary for this buffer
+SEEKABLE_CHECKSUMS = 1                  # cz_seekable_pack_*: the seek table's entries carry the frames' checksums
+# cz_seekable_info (56 bytes)
+SEEKABLE_INFO_DTYPE = np.dtype([("status", "<i4"), ("reason", "<u4"), ("frames", "<u8"), ("frames_bytes", "<u8"), ("content_bytes", "<u8"),
+                                ("stream_bytes", "<u8"), ("detail", "<u8"), ("has_checksums", "<u4"), ("reserved", "<u4")])
+assert SEEKABLE_INFO_DTYPE.itemsize == 56
 
 
 class FrameHeader(C.Structure):
@@ -51,7 +56,7 @@ class BlockHeader(C.Structure):
 
 def build(force: bool = False) -> str:
     """Compile the library in-tree with hipcc for gfx950 (csrc/Makefile)."""
-    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_enc.hip", "czstd_encsplit.hip", "czstd_encfse.hip", "czstd_encfast.hip", "czstd_encfastsplit.hip", "czstd_encrec.hip", "czstd_train.hip", "czstd_types.h", "czstd_dict.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_enc.hip", "czstd_encsplit.hip", "czstd_encfse.hip", "czstd_encfast.hip", "czstd_encfastsplit.hip", "czstd_encrec.hip", "czstd_train.hip", "czstd_seekable.hip", "czstd_seekable_host.h", "czstd_types.h", "czstd_dict.h")]
     srcs += [os.path.join(_HERE, "..", "include", f) for f in ("cairo_zstd_amd.h", "cairo_zstd_amd_status.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -176,6 +181,17 @@ def lib() -> C.CDLL:
     L.cz_dictionary_train_host.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, vp, C.POINTER(sz)]
     L.cz_dictionary_train_last_ms.restype = C.c_int
     L.cz_dictionary_train_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    if hasattr(L, "cz_seekable_bound"):                                 # (diagnostic builds of earlier sources lack them)
+        L.cz_seekable_bound.restype = C.c_uint64
+        L.cz_seekable_bound.argtypes = [C.c_uint64, sz, C.c_uint32]
+        L.cz_seekable_pack_device.restype = C.c_int
+        L.cz_seekable_pack_device.argtypes = [vp, vp, vp, vp, sz, vp, C.c_uint64, C.c_uint32, vp]
+        L.cz_seekable_open_device.restype = C.c_int
+        L.cz_seekable_open_device.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp]
+        L.cz_seekable_pack_host.restype = C.c_int
+        L.cz_seekable_pack_host.argtypes = [vp, vp, vp, sz, vp, C.c_uint64, C.c_uint32, vp]
+        L.cz_seekable_open_host.restype = C.c_int
+        L.cz_seekable_open_host.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp]
     L.cz_partition_balanced.restype = C.c_int
     L.cz_partition_balanced.argtypes = [vp, sz, sz, vp]
     L.cz_decode_batch_multi.restype = C.c_int

@@ -40,6 +40,7 @@
 #include "czstd_encfastsplit.hip" /* cz_compress_fast_plan_kernel, cz_compress_groups_fast_kernel (CZ_COMPRESS_FAST_SPLIT) */
 #include "czstd_encrec.hip"   /* cz_compress_records_kernel, cz_compress_records_dict_kernel (CZ_COMPRESS_RECORDS) */
 #include "czstd_train.hip"    /* cz_train_*_kernel (cz_dictionary_train_*) */
+#include "czstd_seekable.hip" /* cz_seekable_plan_kernel, cz_seekable_gather_kernel, cz_seekable_open_kernel (cz_seekable_*_device) */
 /* the same kernel source once more, without its decoders: cz_execute_frames_kernel (czstd_kernels.hip, CZ_EXEC_ONLY) */
 #define CZ_EXEC_ONLY 1
 namespace czx {
@@ -107,6 +108,9 @@ struct cz_context {
     unsigned long long* encs_plan = nullptr; size_t encs_frames = 0; unsigned long long* encs_counter = nullptr;
     cze_dict_entry* enc_dicts = nullptr; uint32_t enc_dict_count = 0;   /* cz_context_set_compress_dictionaries */
     float train_ms[4] = {0.f, 0.f, 0.f, 0.f};                           /* cz_dictionary_train_last_ms */
+    /* seekable streams: the pack plan (n + 1 scanned offsets and the go word), kept and grown like a scratch; the gather grid; the
+       device copy of cz_seekable_open_device's info */
+    unsigned long long* seek_plan = nullptr; size_t seek_frames = 0; int seek_grid = 0; cz_seekable_info* seek_info = nullptr;
     /* staging for cz_decode_batch_host */
     void* d_stage = nullptr; size_t d_stage_bytes = 0;
     void* h_pin = nullptr; size_t h_pin_bytes = 0;                      /* pinned host staging of cz_decode_batch_multi's share */
@@ -201,6 +205,8 @@ CZ_EXPORT void cz_context_destroy(cz_context* c) {
     if (c->encs_plan) (void)hipFree(c->encs_plan);
     if (c->encs_counter) (void)hipFree(c->encs_counter);
     if (c->enc_dicts) (void)hipFree(c->enc_dicts);
+    if (c->seek_plan) (void)hipFree(c->seek_plan);
+    if (c->seek_info) (void)hipFree(c->seek_info);
     if (c->work_counter) (void)hipFree(c->work_counter);
     if (c->d_stage) (void)hipFree(c->d_stage);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
@@ -1258,6 +1264,57 @@ CZ_EXPORT int cz_dictionary_train_last_ms(cz_context* c, float ms[4]) {
     if (!c || !ms) return CZ_E_INVALID_ARG;
     for (int i = 0; i < 4; i++) ms[i] = c->train_ms[i];
     return CZ_OK;
+}
+
+/* ------------------------------------------------------------------ seekable streams */
+#include "czstd_seekable_host.h"   /* cz_seekable_bound, cz_seekable_pack_host, cz_seekable_open_host: plain C++ */
+
+CZ_EXPORT int cz_seekable_pack_device(cz_context* c, const void* d_frames_base, const uint64_t* d_frame_off, const cz_compress_result* d_results,
+                                      size_t n, void* d_stream, uint64_t stream_cap, uint32_t flags, cz_seekable_info* d_info) {
+    if (!c || (flags & ~CZ_SEEKABLE_CHECKSUMS) || n > CZ_SEEKABLE_MAX_FRAMES || !d_stream || !d_info) return CZ_E_INVALID_ARG;
+    if (n && (!d_frames_base || !d_frame_off || !d_results)) return CZ_E_INVALID_ARG;
+    CZ_HIP(c, hipSetDevice(c->device));
+    if (!c->seek_plan || c->seek_frames < n) {                          /* (launches in flight may still use the old one) */
+        if (c->seek_plan) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->seek_plan); c->seek_plan = nullptr; c->seek_frames = 0; }
+        CZ_HIP(c, hipMalloc((void**)&c->seek_plan, (n + 2) * sizeof(unsigned long long)));
+        c->seek_frames = n;
+    }
+    hipLaunchKernelGGL(cz_seekable_plan_kernel, dim3(1), dim3(CZS_THREADS), 0, c->stream, d_results, (uint32_t)n, flags, stream_cap, c->seek_plan, d_info);
+    CZ_HIP(c, hipGetLastError());
+    /* a persistent grid over the tiles of the destination: as many workgroups as the device holds, no more than stream_cap has tiles */
+    cz_seekable_gather_args a; memset(&a, 0, sizeof a);
+    a.frames_base = (const uint8_t*)d_frames_base; a.frame_off = d_frame_off; a.results = d_results; a.plan = c->seek_plan;
+    a.stream = (uint8_t*)d_stream; a.n = (uint32_t)n; a.flags = flags;
+    if (!c->seek_grid) {
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_seekable_gather_kernel, CZS_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
+        c->seek_grid = c->num_cu * occ;
+    }
+    const uint64_t need = cz_seekable_bound(0, n, flags), cap = stream_cap > need ? stream_cap : need;
+    const uint64_t tiles = (cap + 15 + 16ull * CZS_TILE_VECS) / (16ull * CZS_TILE_VECS);
+    const unsigned grid = tiles < (uint64_t)c->seek_grid ? (unsigned)tiles : (unsigned)c->seek_grid;
+    hipLaunchKernelGGL(cz_seekable_gather_kernel, dim3(grid), dim3(CZS_THREADS), 0, c->stream, a);
+    CZ_HIP(c, hipGetLastError());
+    return CZ_OK;
+}
+
+CZ_EXPORT int cz_seekable_open_device(cz_context* c, const void* d_stream, uint64_t stream_len, uint64_t first, uint64_t count, uint32_t out_align,
+                                      uint64_t* d_in_off, uint64_t* d_in_len, uint64_t* d_out_off, uint64_t* d_out_cap, uint32_t* d_checksum,
+                                      cz_seekable_info* info) {
+    if (!info) return CZ_E_INVALID_ARG;
+    memset(info, 0, sizeof *info);
+    info->status = CZ_E_INVALID_ARG;
+    if (!c || out_align == 0 || out_align > 4096 || (out_align & (out_align - 1)) || (!d_stream && stream_len)) return CZ_E_INVALID_ARG;
+    CZ_HIP(c, hipSetDevice(c->device));
+    if (!c->seek_info) CZ_HIP(c, hipMalloc((void**)&c->seek_info, 256));
+    cz_seekable_open_args a; memset(&a, 0, sizeof a);
+    a.stream = (const uint8_t*)d_stream; a.stream_len = stream_len; a.first = first; a.count = count; a.out_align = out_align;
+    a.in_off = d_in_off; a.in_len = d_in_len; a.out_off = d_out_off; a.out_cap = d_out_cap; a.checksum = d_checksum; a.info = c->seek_info;
+    hipLaunchKernelGGL(cz_seekable_open_kernel, dim3(1), dim3(CZS_THREADS), 0, c->stream, a);
+    CZ_HIP(c, hipGetLastError());
+    CZ_HIP(c, hipMemcpyAsync(info, c->seek_info, sizeof *info, hipMemcpyDeviceToHost, c->stream));
+    CZ_HIP(c, hipStreamSynchronize(c->stream));
+    return info->status;
 }
 
 /* ------------------------------------------------------------------ several devices */

@@ -602,6 +602,71 @@ int cz_dictionary_train_host(cz_context* ctx, const void* base, size_t bytes, co
 /* Milliseconds on the device of the last training's four steps: frequencies, epochs, statistics, tables and header. */
 int cz_dictionary_train_last_ms(cz_context* ctx, float ms[4]);
 
+/* ---- seekable streams ----
+ * A batch of frames as ONE stream: the frames back to back, then one skippable frame, the seek table of the zstd seekable format,
+ * that lists every frame's compressed and decompressed size (all fields little-endian, nothing aligned):
+ *     frame 0 | ... | frame n-1 | 0x184D2A5E (4) | Frame_Size = n * E + 9 (4) | n entries of E bytes | footer (9)
+ *     entry  = Compressed_Size (4), Decompressed_Size (4), [Checksum (4): low 32 bits of XXH64 of the decompressed bytes]
+ *     footer = Number_Of_Frames (4), Seek_Table_Descriptor (1), 0x8F92EAB1 (4)
+ * E is 8 without checksums and 12 with them.  Descriptor: bit 7 Checksum_Flag; bits 6..2 reserved, written as 0 and refused when
+ * set; bits 1..0 unused, written as 0 and ignored.  Number_Of_Frames is at most CZ_SEEKABLE_MAX_FRAMES, and the frames listed cover
+ * the stream from byte 0 to the table's first byte exactly.  Every zstd decoder reads such a stream (it skips the table; so do
+ * cz_stream_split and cz_decode_stream); with the table, cutting the stream into a batch is two prefix sums, done on the device.
+ */
+#define CZ_SEEKABLE_CHECKSUMS 1u            /* flag: entries carry the checksum (cz_compress_result.checksum) */
+#define CZ_SEEKABLE_MAX_FRAMES 0x8000000u
+typedef struct cz_seekable_info {
+    int32_t  status;        /* CZ_OK | CZ_E_SEEK_TABLE | CZ_E_INVALID_ARG | CZ_E_OUTPUT_TOO_SMALL */
+    uint32_t reason;        /* CZ_E_SEEK_TABLE: the first check that failed, in the order below; else 0 */
+    uint64_t frames;        /* Number_Of_Frames (pack: n) */
+    uint64_t frames_bytes;  /* sum of Compressed_Size = offset of the seek table */
+    uint64_t content_bytes; /* sum of Decompressed_Size over all frames */
+    uint64_t stream_bytes;  /* frames_bytes + 8 + frames * E + 9 */
+    uint64_t detail;
+    uint32_t has_checksums, reserved;
+} cz_seekable_info;
+/* frame_bytes + 8 + n * E + 9: the stream of n frames of frame_bytes bytes together (flags: CZ_SEEKABLE_CHECKSUMS or 0). */
+uint64_t cz_seekable_bound(uint64_t frame_bytes, size_t n, uint32_t flags);
+/* Packs the output of any cz_compress_batch_* call as it lies: frame i is d_results[i].bytes_written bytes at d_frames_base +
+ * d_frame_off[i], its Decompressed_Size is bytes_read, its Checksum is checksum.  All pointers are DEVICE pointers, d_info included.
+ * Asynchronous on the context's stream and never synchronises: enqueued behind a compress launch of the same context it needs no
+ * host step in between.  Returns CZ_E_INVALID_ARG for a flag bit other than CZ_SEEKABLE_CHECKSUMS, n above CZ_SEEKABLE_MAX_FRAMES or a
+ * NULL pointer (n == 0: d_stream and d_info only are needed; the stream is the 17-byte table).  What depends on device data is decided on
+ * the device (cz_seekable_plan_kernel) and reported in d_info->status:
+ *   CZ_E_INVALID_ARG       a record with status != CZ_OK, with bytes_written or bytes_read of 2^32 or more, or (with
+ *                          CZ_SEEKABLE_CHECKSUMS) with result flags that lack CZ_COMPRESS_CHECKSUM; detail = the lowest such index,
+ *                          frames = n, the three sums are 0
+ *   CZ_E_OUTPUT_TOO_SMALL  stream_bytes > stream_cap; stream_bytes and the other sums still report the need
+ * On either error no byte of d_stream is touched; on success no byte past stream_bytes (and none in front of d_stream).  A frame's
+ * slot is never read outside [0, bytes_written).  Source and stream must not overlap.  The bytes depend on the frames, their sizes
+ * and flags alone. */
+int cz_seekable_pack_device(cz_context* ctx, const void* d_frames_base, const uint64_t* d_frame_off, const cz_compress_result* d_results,
+                            size_t n, void* d_stream, uint64_t stream_cap, uint32_t flags, cz_seekable_info* d_info);
+/* Validates the table of the stream in HBM and writes, for frames [first, first + count), the four arrays that go into
+ * cz_decode_batch_device unchanged (DEVICE pointers, count entries each): in_off absolute in the stream, in_len = Compressed_Size,
+ * out_cap = Decompressed_Size, out_off = the exclusive sum of the range's out_cap each rounded up to out_align (the first frame of
+ * the range at 0).  d_checksum (may be NULL) gets the entries' checksums, zeros when the table has none.  Any of the array pointers
+ * may be NULL; with all five NULL the call only fills *info (the sizing call).  count == UINT64_MAX: up to the end.  `info` is a HOST
+ * pointer; the call synchronises the context's stream (it is set-up, like cz_context_measure_batch) and returns info->status:
+ *   CZ_E_INVALID_ARG  out_align not a power of two from 1 to 4096 or a NULL ctx / info / stream (decided on the host, nothing
+ *                     launched), first > frames or first + count > frames (the table's fields are reported)
+ *   CZ_E_SEEK_TABLE   reason = the first check that failed: 1 stream shorter than 17 bytes, 2 Seekable_Magic_Number wrong,
+ *                     3 reserved descriptor bits set, 4 Number_Of_Frames above the maximum or a table longer than the stream,
+ *                     5 Skippable_Magic_Number or Frame_Size at the computed table start wrong, 6 sum of Compressed_Size != table
+ *                     offset; every other field of *info is 0
+ * On any error no array is written.  info->detail = the output bytes the range needs (the last out_off plus the last out_cap; 0 for
+ * an empty range). */
+int cz_seekable_open_device(cz_context* ctx, const void* d_stream, uint64_t stream_len, uint64_t first, uint64_t count, uint32_t out_align,
+                            uint64_t* d_in_off, uint64_t* d_in_len, uint64_t* d_out_off, uint64_t* d_out_cap, uint32_t* d_checksum,
+                            cz_seekable_info* info);
+/* The same two calls with HOST buffers and arrays, in plain C++ on the CPU (csrc/czstd_seekable_host.h; no device, no context, like
+ * cz_stream_split): the library's second implementation of the format, which the kernels are held to.  Both return info->status. */
+int cz_seekable_pack_host(const void* frames_base, const uint64_t* frame_off, const cz_compress_result* results, size_t n,
+                          void* stream, uint64_t stream_cap, uint32_t flags, cz_seekable_info* info);
+int cz_seekable_open_host(const void* stream, uint64_t stream_len, uint64_t first, uint64_t count, uint32_t out_align,
+                          uint64_t* in_off, uint64_t* in_len, uint64_t* out_off, uint64_t* out_cap, uint32_t* checksum,
+                          cz_seekable_info* info);
+
 #ifdef __cplusplus
 }
 #endif

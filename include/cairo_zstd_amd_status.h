@@ -123,7 +123,8 @@ typedef enum cz_status {
     CZ_E_NOT_FINISHED = 905,       /* frame ran out of source before its last block */
     CZ_E_OUT_OF_MEMORY = 906,      /* a host allocation failed inside the library (std::bad_alloc does not cross the C ABI) */
     CZ_E_DICT_UNKNOWN = 907,       /* the frame's Dictionary_ID names none of the dictionaries cz_context_set_dictionaries registered; detail[0] = the ID */
-    CZ_E_WAIT_EXPIRED = 908        /* a device-side wait ran into its bound; no reference analogue */
+    CZ_E_WAIT_EXPIRED = 908,       /* a device-side wait ran into its bound; no reference analogue */
+    CZ_E_SEEK_TABLE = 909          /* the seek table of a seekable stream is malformed; cz_seekable_info.reason says which check failed */
 } cz_status;
 
 #ifdef __cplusplus
