@@ -14,6 +14,8 @@ Python here is a thin mirror over the C ABI (include/cairo_zstd_amd.h, libcairo_
   * train_dictionary / Context.train_dictionary_device : a zstd dictionary made from samples on the device
   * Context.seekable_pack_device / Context.seekable_open_device / decode_seekable : a batch of frames as one seekable stream (the
     frames back to back and a seek table), packed and opened on the device; pack_seekable / open_seekable: the same on the CPU
+  * Context.seekable_index / SeekableIndex.locate / Context.seekable_gather_device / read_seekable : byte ranges of such a stream's
+    content, decoding only the frames they touch; locate_seekable: the locate on the CPU
 All decoding and compression runs in the HIP kernels; nothing here decodes or compresses on the CPU.
 """
 from __future__ import annotations
@@ -24,7 +26,7 @@ import weakref
 import numpy as np
 
 from . import status
-from ._lib import (COMPRESS_CHECKSUM, COMPRESS_FAST, COMPRESS_FAST_SPLIT, COMPRESS_RECORDS, COMPRESS_FSE_TABLES, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, COMPRESS_SPLIT, SEEKABLE_CHECKSUMS, SEEKABLE_INFO_DTYPE, TRAIN_MIN_CAPACITY, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
+from ._lib import (COMPRESS_CHECKSUM, COMPRESS_FAST, COMPRESS_FAST_SPLIT, COMPRESS_RECORDS, COMPRESS_FSE_TABLES, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, COMPRESS_SPLIT, SEEKABLE_CHECKSUMS, SEEKABLE_INFO_DTYPE, SEEKABLE_READ_INFO_DTYPE, SEEKABLE_SPAN_DTYPE, TRAIN_MIN_CAPACITY, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
                    BlockHeader, FrameHeader, build, lib)
 
 DEBUG_CHAIN_CPP_STEP, DEBUG_NO_HUF1, DEBUG_WX_POISON, DEBUG_EXEC_FIRST, DEBUG_EXEC_LEAVE = 1, 2, 4, 8, 16     # cz_context_set_debug_flags
@@ -35,7 +37,8 @@ __all__ = ["Context", "FrameDecoder", "BlockDecodingStrategy", "decode_batch_hos
            "RESULT_CHECKSUM_MATCH", "status", "CzError", "build", "lib", "compress_bound", "compress_batch_host", "compress",
            "COMPRESS_CHECKSUM", "COMPRESS_RESULT_DTYPE", "compress_batch_host_dict", "COMPRESS_NO_DICT", "COMPRESS_NO_DICT_ID",
            "COMPRESS_SPLIT", "compress_split_segment", "COMPRESS_FSE_TABLES", "COMPRESS_FAST", "COMPRESS_FAST_SPLIT", "COMPRESS_RECORDS", "compress_record_max", "train_dictionary", "TRAIN_MIN_CAPACITY",
-           "SEEKABLE_CHECKSUMS", "SEEKABLE_INFO_DTYPE", "seekable_bound", "pack_seekable", "open_seekable", "decode_seekable"]
+           "SEEKABLE_CHECKSUMS", "SEEKABLE_INFO_DTYPE", "seekable_bound", "pack_seekable", "open_seekable", "decode_seekable",
+           "SEEKABLE_READ_INFO_DTYPE", "SEEKABLE_SPAN_DTYPE", "SeekableIndex", "locate_seekable", "read_seekable"]
 
 
 def _as_u8(b) -> np.ndarray:
@@ -64,7 +67,7 @@ class Context:
 
     def close(self):
         if getattr(self, "_h", None):
-            for fd in list(self._decoders):      # frame decoders hold device memory of this context
+            for fd in list(self._decoders):      # frame decoders and seekable indexes hold device memory of this context
                 fd.close()
             lib().cz_context_destroy(self._h)
             self._h = None
@@ -98,6 +101,7 @@ class Context:
     def set_verify_checksum(self, on: bool = True):
         """Compute and compare the XXH64 content checksum of every checksummed frame on the device."""
         lib().cz_context_set_verify_checksum(self._h, 1 if on else 0)
+        self._verify = bool(on)
 
     def set_dictionary(self, dictionary: "Dictionary | None"):
         """Batch decodes start every frame from `dictionary` (None: from nothing): init_from_dict, src/decoding/scratch.cairo:60-65."""
@@ -407,6 +411,22 @@ class Context:
             raise CzError(st, f"cz_seekable_open_device (hip error {lib().cz_context_last_hip_error(self._h)})")
         return info[0]
 
+    def seekable_index(self, stream: int, stream_len: int) -> "SeekableIndex":
+        """cz_seekable_index_create_device: the index of the stream at the DEVICE pointer `stream` (its table validated as by
+        seekable_open_device; the scans of its sizes and its checksums kept in HBM).  Synchronises; the stream need not outlive the
+        call.  Raises CzError on a malformed table (with the reason)."""
+        return SeekableIndex(self, stream, stream_len)
+
+    def seekable_gather_device(self, decoded: int, out_off: int, content_off: int, k: int, range_off: int, range_len: int, spans: int,
+                               m: int, dst: int, dst_bytes: int):
+        """cz_seekable_gather_device: the m ranges out of the k decoded frames of one SeekableIndex.locate (its arrays, as raw DEVICE
+        pointers) back to back into `dst`.  Asynchronous on the context's stream and never synchronises: directly behind the
+        decode launch it needs no host step in between."""
+        st = lib().cz_seekable_gather_device(self._h, decoded or None, out_off or None, content_off or None, k, range_off or None,
+                                             range_len or None, spans or None, m, dst or None, dst_bytes)
+        if st:
+            raise CzError(st, f"cz_seekable_gather_device (hip error {lib().cz_context_last_hip_error(self._h)})")
+
     def last_train_ms(self):
         """cz_dictionary_train_last_ms: device milliseconds of the last training's steps (frequencies, epochs, statistics, tables)."""
         ms = (C.c_float * 4)()
@@ -509,6 +529,133 @@ def decode_seekable(stream, ctx: Context, first: int = 0, count: int | None = No
         if int(res[i]["status"]):
             raise CzError(int(res[i]["status"]), f"frame {first + i}")
     return [out[int(off[i]): int(off[i]) + int(res[i]["bytes_produced"])].tobytes() for i in range(k)]
+
+
+class SeekableIndex:
+    """cz_seekable_index: a seekable stream's table, validated and scanned once, in HBM (Context.seekable_index).  `.info` is the
+    SEEKABLE_INFO_DTYPE record of the table."""
+
+    def __init__(self, ctx: Context, stream: int, stream_len: int):
+        self._h = None
+        info = np.zeros(1, dtype=SEEKABLE_INFO_DTYPE)
+        h = C.c_void_p()
+        st = lib().cz_seekable_index_create_device(ctx._h, stream or None, stream_len, C.byref(h), info.ctypes.data)
+        if st == status.CZ_E_HIP:
+            raise CzError(st, f"cz_seekable_index_create_device (hip error {lib().cz_context_last_hip_error(ctx._h)})")
+        if st:
+            raise CzError(st, f"cz_seekable_index_create_device (reason {int(info[0]['reason'])})")
+        self._h, self.ctx, self.info = h, ctx, info[0]
+        ctx._decoders.add(self)
+
+    def locate(self, range_off: int, range_len: int, m: int, out_align: int = 1, frames_cap: int = 0, frame: int = 0, in_off: int = 0,
+               in_len: int = 0, out_off: int = 0, out_cap: int = 0, checksum: int = 0, content_off: int = 0, spans: int = 0):
+        """cz_seekable_locate_device: which frames hold a byte of the m ranges at the DEVICE pointers range_off / range_len, and
+        where each range lies in their decode output.  The arrays go to the DEVICE pointers given (0: not wanted; all 0: the sizing
+        call).  Synchronises.  Returns the SEEKABLE_READ_INFO_DTYPE record: status (CZ_OK; CZ_E_INVALID_ARG with the lowest index of
+        a range outside the content in `detail`; CZ_E_OUTPUT_TOO_SMALL when more than frames_cap frames are selected), `selected`,
+        `out_bytes` and `dst_bytes`."""
+        info = np.zeros(1, dtype=SEEKABLE_READ_INFO_DTYPE)
+        st = lib().cz_seekable_locate_device(self._h, range_off or None, range_len or None, m, out_align, frames_cap, frame or None,
+                                             in_off or None, in_len or None, out_off or None, out_cap or None, checksum or None,
+                                             content_off or None, spans or None, info.ctypes.data)
+        if st == status.CZ_E_HIP:
+            raise CzError(st, f"cz_seekable_locate_device (hip error {lib().cz_context_last_hip_error(self.ctx._h)})")
+        return info[0]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().cz_seekable_index_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def locate_seekable(stream, ranges, out_align: int = 1):
+    """cz_seekable_locate_host (on the CPU, no device): (info, frame, in_off, in_len, out_off, out_cap, checksums, content_off, spans)
+    for `ranges`, a list of (offset, length) in the content of the seekable stream: the frames that hold a requested byte, as
+    decode_batch_* take them, and per range a SEEKABLE_SPAN_DTYPE record.  `info` is the SEEKABLE_READ_INFO_DTYPE record; when its
+    status is not CZ_OK (CZ_E_SEEK_TABLE with the reason, CZ_E_INVALID_ARG with the range in `detail`) the arrays are empty."""
+    a = _as_u8(stream)
+    m = len(ranges)
+    r = np.array(ranges, dtype=np.uint64).reshape(m, 2)
+    off, ln = np.ascontiguousarray(r[:, 0]), np.ascontiguousarray(r[:, 1])
+    info = np.zeros(1, dtype=SEEKABLE_READ_INFO_DTYPE)
+    args = (a.ctypes.data if a.size else None, a.size, off.ctypes.data if m else None, ln.ctypes.data if m else None, m, out_align)
+    st = lib().cz_seekable_locate_host(*args, 0, None, None, None, None, None, None, None, None, info.ctypes.data)
+    k = 0 if st else int(info[0]["selected"])
+    arr = [np.zeros(k, dtype=t) for t in (np.uint32, np.uint64, np.uint64, np.uint64, np.uint64, np.uint32, np.uint64)]
+    spans = np.zeros(0 if st else m, dtype=SEEKABLE_SPAN_DTYPE)
+    if not st:
+        lib().cz_seekable_locate_host(*args, k, *[x.ctypes.data if k else None for x in arr], spans.ctypes.data if m else None, info.ctypes.data)
+    return (info[0], *arr, spans)
+
+
+def read_seekable(stream_or_index, ctx: Context, ranges, verify: bool = False, stream=None):
+    """The bytes of `ranges`, a list of (offset, length) in the content of a seekable stream: a list of bytes, one per range.  Only
+    the frames that hold a requested byte are decoded: the stream is staged in HBM, then index (unless a SeekableIndex is given, with
+    the staged stream it was made from as the torch tensor `stream`), locate as a sizing call, locate, ONE decode_batch_device of the
+    k frames, the gather and one copy back.  verify=True: the context verifies the frames' checksums, and where the table carries
+    checksums they must equal the calculated ones.  Raises CzError on a malformed table, a range outside the content, a frame that
+    fails (named by its number in the stream) or a checksum that differs."""
+    import torch
+    dev = torch.device(f"cuda:{ctx.device}")
+    m = len(ranges)
+    r = np.array(ranges, dtype=np.uint64).reshape(m, 2)
+    if isinstance(stream_or_index, SeekableIndex):
+        ix, own, d_stream = stream_or_index, False, stream
+        if d_stream is None:
+            raise CzError(status.CZ_E_INVALID_ARG, "read_seekable with a SeekableIndex needs the staged stream (stream=)")
+    else:
+        a = _as_u8(stream_or_index)
+        d_stream = torch.zeros(a.size + 64, dtype=torch.uint8, device=dev)
+        d_stream[:a.size] = torch.from_numpy(a.copy())
+        torch.cuda.synchronize(dev)
+        ix, own = ctx.seekable_index(d_stream.data_ptr(), a.size), True
+    was = getattr(ctx, "_verify", False)
+    try:
+        d_rng = torch.from_numpy(np.ascontiguousarray(r.T).view(np.int64).copy()).to(dev) if m else torch.zeros((2, 1), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        rp = (d_rng[0].data_ptr(), d_rng[1].data_ptr(), m) if m else (0, 0, 0)
+        size = ix.locate(*rp, 256)
+        if int(size["status"]):
+            raise CzError(int(size["status"]), f"cz_seekable_locate_device (range {int(size['detail'])})")
+        k, dst_bytes = int(size["selected"]), int(size["dst_bytes"])
+        if k == 0:
+            return [b""] * m
+        desc = torch.zeros((5, k), dtype=torch.int64, device=dev)       # in_off, in_len, out_off, out_cap, content_off
+        d_u32 = torch.zeros((2, k), dtype=torch.int32, device=dev)      # frame, checksum
+        d_spans = torch.zeros(m * SEEKABLE_SPAN_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_out = torch.zeros(int(size["out_bytes"]) + 256, dtype=torch.uint8, device=dev)
+        d_res = torch.zeros(k * RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_dst = torch.zeros(dst_bytes + 16, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        info = ix.locate(*rp, 256, k, d_u32[0].data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), desc[2].data_ptr(), desc[3].data_ptr(),
+                         d_u32[1].data_ptr(), desc[4].data_ptr(), d_spans.data_ptr())
+        if int(info["status"]):
+            raise CzError(int(info["status"]), "cz_seekable_locate_device")
+        if verify:
+            ctx.set_verify_checksum(True)
+        ctx.decode_batch_device(d_stream.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), k, d_out.data_ptr(), desc[2].data_ptr(),
+                                desc[3].data_ptr(), d_res.data_ptr())
+        ctx.seekable_gather_device(d_out.data_ptr(), desc[2].data_ptr(), desc[4].data_ptr(), k, rp[0], rp[1], d_spans.data_ptr(), m,
+                                   d_dst.data_ptr(), dst_bytes)
+        ctx.synchronize()
+        res = d_res.cpu().numpy().view(RESULT_DTYPE)
+        u32 = d_u32.cpu().numpy().view(np.uint32)
+        for s in np.flatnonzero(res["status"] != 0)[:1]:
+            raise CzError(int(res[s]["status"]), f"frame {int(u32[0][s])}")
+        if verify and int(info["has_checksums"]):
+            ok = ((res["flags"] & RESULT_CHECKSUM_COMPUTED) != 0) & (res["calculated_checksum"] == u32[1])
+            for s in np.flatnonzero(~ok)[:1]:
+                raise CzError(status.CZ_E_SEEK_TABLE, f"frame {int(u32[0][s])}: the table's checksum differs from the calculated one")
+        out = d_dst.cpu().numpy()
+        at = np.concatenate([[0], np.cumsum(r[:, 1])]).astype(np.uint64)
+        return [out[int(at[j]): int(at[j + 1])].tobytes() for j in range(m)]
+    finally:
+        if verify:
+            ctx.set_verify_checksum(was)
+        if own:
+            ix.close()
 
 
 def _compress_flags(checksum, split, fse_tables, fast=False, records=False, fast_split=False) -> int:

@@ -36,6 +36,11 @@ SEEKABLE_CHECKSUMS = 1                  # cz_seekable_pack_*: the seek table's e
 SEEKABLE_INFO_DTYPE = np.dtype([("status", "<i4"), ("reason", "<u4"), ("frames", "<u8"), ("frames_bytes", "<u8"), ("content_bytes", "<u8"),
                                 ("stream_bytes", "<u8"), ("detail", "<u8"), ("has_checksums", "<u4"), ("reserved", "<u4")])
 assert SEEKABLE_INFO_DTYPE.itemsize == 56
+# cz_seekable_read_info (64 bytes) and cz_seekable_span (24 bytes) of cz_seekable_locate_*
+SEEKABLE_READ_INFO_DTYPE = np.dtype([("status", "<i4"), ("reason", "<u4"), ("frames", "<u8"), ("content_bytes", "<u8"), ("selected", "<u8"),
+                                     ("out_bytes", "<u8"), ("dst_bytes", "<u8"), ("detail", "<u8"), ("has_checksums", "<u4"), ("reserved", "<u4")])
+SEEKABLE_SPAN_DTYPE = np.dtype([("dst_off", "<u8"), ("src_off", "<u8"), ("sel_first", "<u4"), ("sel_count", "<u4")])
+assert SEEKABLE_READ_INFO_DTYPE.itemsize == 64 and SEEKABLE_SPAN_DTYPE.itemsize == 24
 
 
 class FrameHeader(C.Structure):
@@ -56,7 +61,7 @@ class BlockHeader(C.Structure):
 
 def build(force: bool = False) -> str:
     """Compile the library in-tree with hipcc for gfx950 (csrc/Makefile)."""
-    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_enc.hip", "czstd_encsplit.hip", "czstd_encfse.hip", "czstd_encfast.hip", "czstd_encfastsplit.hip", "czstd_encrec.hip", "czstd_train.hip", "czstd_seekable.hip", "czstd_seekable_host.h", "czstd_types.h", "czstd_dict.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_enc.hip", "czstd_encsplit.hip", "czstd_encfse.hip", "czstd_encfast.hip", "czstd_encfastsplit.hip", "czstd_encrec.hip", "czstd_train.hip", "czstd_seekable.hip", "czstd_seekable_host.h", "czstd_seekable_read.hip", "czstd_seekable_read_host.h", "czstd_types.h", "czstd_dict.h")]
     srcs += [os.path.join(_HERE, "..", "include", f) for f in ("cairo_zstd_amd.h", "cairo_zstd_amd_status.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -192,6 +197,19 @@ def lib() -> C.CDLL:
         L.cz_seekable_pack_host.argtypes = [vp, vp, vp, sz, vp, C.c_uint64, C.c_uint32, vp]
         L.cz_seekable_open_host.restype = C.c_int
         L.cz_seekable_open_host.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "cz_seekable_locate_device"):                         # (diagnostic builds of earlier sources lack them)
+        L.cz_seekable_index_create_device.restype = C.c_int
+        L.cz_seekable_index_create_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp), vp]
+        L.cz_seekable_index_destroy.restype = None
+        L.cz_seekable_index_destroy.argtypes = [vp]
+        L.cz_seekable_locate_device.restype = C.c_int
+        L.cz_seekable_locate_device.argtypes = [vp, vp, vp, sz, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cz_seekable_gather_device.restype = C.c_int
+        L.cz_seekable_gather_device.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, sz, vp, C.c_uint64]
+        L.cz_seekable_locate_host.restype = C.c_int
+        L.cz_seekable_locate_host.argtypes = [vp, C.c_uint64, vp, vp, sz, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cz_seekable_gather_host.restype = C.c_int
+        L.cz_seekable_gather_host.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, vp, sz, vp, C.c_uint64]
     L.cz_partition_balanced.restype = C.c_int
     L.cz_partition_balanced.argtypes = [vp, sz, sz, vp]
     L.cz_decode_batch_multi.restype = C.c_int

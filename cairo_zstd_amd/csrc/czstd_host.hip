@@ -41,6 +41,7 @@
 #include "czstd_encrec.hip"   /* cz_compress_records_kernel, cz_compress_records_dict_kernel (CZ_COMPRESS_RECORDS) */
 #include "czstd_train.hip"    /* cz_train_*_kernel (cz_dictionary_train_*) */
 #include "czstd_seekable.hip" /* cz_seekable_plan_kernel, cz_seekable_gather_kernel, cz_seekable_open_kernel (cz_seekable_*_device) */
+#include "czstd_seekable_read.hip" /* cz_seekable_index_kernel, cz_seekable_locate_kernel, cz_seekable_select_kernel, cz_seekable_ranges_kernel */
 /* the same kernel source once more, without its decoders: cz_execute_frames_kernel (czstd_kernels.hip, CZ_EXEC_ONLY) */
 #define CZ_EXEC_ONLY 1
 namespace czx {
@@ -111,6 +112,7 @@ struct cz_context {
     /* seekable streams: the pack plan (n + 1 scanned offsets and the go word), kept and grown like a scratch; the gather grid; the
        device copy of cz_seekable_open_device's info */
     unsigned long long* seek_plan = nullptr; size_t seek_frames = 0; int seek_grid = 0; cz_seekable_info* seek_info = nullptr;
+    int seek_read_grid = 0;                                             /* the grid of cz_seekable_ranges_kernel */
     /* staging for cz_decode_batch_host */
     void* d_stage = nullptr; size_t d_stage_bytes = 0;
     void* h_pin = nullptr; size_t h_pin_bytes = 0;                      /* pinned host staging of cz_decode_batch_multi's share */
@@ -1315,6 +1317,111 @@ CZ_EXPORT int cz_seekable_open_device(cz_context* c, const void* d_stream, uint6
     CZ_HIP(c, hipMemcpyAsync(info, c->seek_info, sizeof *info, hipMemcpyDeviceToHost, c->stream));
     CZ_HIP(c, hipStreamSynchronize(c->stream));
     return info->status;
+}
+
+/* ------------------------------------------------------------------ byte ranges out of a seekable stream */
+#include "czstd_seekable_read_host.h"   /* cz_seekable_locate_host, cz_seekable_gather_host: plain C++ */
+
+/* One allocation: a head of 256 bytes (the bad-range word, then at byte 64 the device copy of the locate's info), comp[n + 1],
+   cont[n + 1], sel_off[n], sums[n], reach[n].  rng: (first frame, last frame + 1) per range, kept and grown like a scratch. */
+struct cz_seekable_index {
+    cz_context* ctx = nullptr; uint64_t n = 0; uint32_t has_checksums = 0;
+    uint8_t* block = nullptr; unsigned long long* comp = nullptr; unsigned long long* cont = nullptr; unsigned long long* sel_off = nullptr;
+    uint32_t* sums = nullptr; uint32_t* reach = nullptr; uint32_t* rng = nullptr; size_t rng_ranges = 0;
+};
+
+CZ_EXPORT void cz_seekable_index_destroy(cz_seekable_index* ix) {
+    if (!ix) return;
+    if (ix->ctx) (void)hipSetDevice(ix->ctx->device);
+    if (ix->block) (void)hipFree(ix->block);
+    if (ix->rng) (void)hipFree(ix->rng);
+    delete ix;
+}
+
+CZ_EXPORT int cz_seekable_index_create_device(cz_context* c, const void* d_stream, uint64_t stream_len, cz_seekable_index** out, cz_seekable_info* info) {
+    if (out) *out = nullptr;
+    if (!info) return CZ_E_INVALID_ARG;
+    if (!out) { memset(info, 0, sizeof *info); return info->status = CZ_E_INVALID_ARG; }
+    /* an open of no frames: the table's validation and *info are cz_seekable_open_kernel's */
+    const int st = cz_seekable_open_device(c, d_stream, stream_len, 0, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, info);
+    if (st != CZ_OK) return st;
+    cz_seekable_index* ix = new (std::nothrow) cz_seekable_index;
+    if (!ix) return info->status = CZ_E_OUT_OF_MEMORY;
+    const uint64_t n = info->frames;
+    ix->ctx = c; ix->n = n; ix->has_checksums = info->has_checksums;
+    hipError_t e = hipMalloc((void**)&ix->block, 256 + (n + 1) * 16 + n * 16);
+    if (e == hipSuccess) e = hipMemsetAsync(ix->block, 0, 256, c->stream);
+    if (e == hipSuccess) {
+        ix->comp = (unsigned long long*)(ix->block + 256); ix->cont = ix->comp + (n + 1); ix->sel_off = ix->cont + (n + 1);
+        ix->sums = (uint32_t*)(ix->sel_off + n); ix->reach = ix->sums + n;
+        cz_seekable_index_args a; memset(&a, 0, sizeof a);
+        a.stream = (const uint8_t*)d_stream; a.stream_len = stream_len; a.n = n; a.E = info->has_checksums ? 12u : 8u;
+        a.comp = ix->comp; a.cont = ix->cont; a.sums = ix->sums; a.reach = ix->reach;
+        hipLaunchKernelGGL(cz_seekable_index_kernel, dim3(1), dim3(CZS_THREADS), 0, c->stream, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { c->last_hip_error = (int)e; c->last_hip_line = __LINE__; cz_seekable_index_destroy(ix); return info->status = CZ_E_HIP; }
+    *out = ix;
+    return CZ_OK;
+}
+
+CZ_EXPORT int cz_seekable_locate_device(cz_seekable_index* ix, const uint64_t* d_range_off, const uint64_t* d_range_len, size_t m,
+                                        uint32_t out_align, uint64_t frames_cap,
+                                        uint32_t* d_frame, uint64_t* d_in_off, uint64_t* d_in_len, uint64_t* d_out_off, uint64_t* d_out_cap,
+                                        uint32_t* d_checksum, uint64_t* d_content_off, cz_seekable_span* d_spans, cz_seekable_read_info* info) {
+    if (!info) return CZ_E_INVALID_ARG;
+    memset(info, 0, sizeof *info);
+    info->status = CZ_E_INVALID_ARG;
+    if (!ix || out_align == 0 || out_align > 4096 || (out_align & (out_align - 1)) || m > CZ_SEEKABLE_MAX_FRAMES || (m && (!d_range_off || !d_range_len))) return CZ_E_INVALID_ARG;
+    cz_context* c = ix->ctx;
+    CZ_HIP(c, hipSetDevice(c->device));
+    if (ix->rng_ranges < m) {                                           /* (launches in flight may still use the old one) */
+        if (ix->rng) { CZ_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(ix->rng); ix->rng = nullptr; ix->rng_ranges = 0; }
+        CZ_HIP(c, hipMalloc((void**)&ix->rng, m * 2 * sizeof(uint32_t)));
+        ix->rng_ranges = m;
+    }
+    uint32_t* bad = (uint32_t*)ix->block; cz_seekable_read_info* d_info = (cz_seekable_read_info*)(ix->block + 64);
+    if (m) {
+        cz_seekable_locate_args a; memset(&a, 0, sizeof a);
+        a.cont = ix->cont; a.n = ix->n; a.range_off = d_range_off; a.range_len = d_range_len; a.m = m; a.reach = ix->reach; a.rng = ix->rng; a.bad = bad;
+        hipLaunchKernelGGL(cz_seekable_locate_kernel, dim3((unsigned)((m + CZS_THREADS - 1) / CZS_THREADS)), dim3(CZS_THREADS), 0, c->stream, a);
+        CZ_HIP(c, hipGetLastError());
+    }
+    cz_seekable_select_args s; memset(&s, 0, sizeof s);
+    s.comp = ix->comp; s.cont = ix->cont; s.sums = ix->sums; s.reach = ix->reach; s.sel_off = ix->sel_off; s.rng = ix->rng; s.bad = bad;
+    s.n = ix->n; s.has_checksums = ix->has_checksums; s.out_align = out_align; s.frames_cap = frames_cap;
+    s.range_off = d_range_off; s.range_len = d_range_len; s.m = m;
+    s.frame = d_frame; s.in_off = d_in_off; s.in_len = d_in_len; s.out_off = d_out_off; s.out_cap = d_out_cap; s.checksum = d_checksum;
+    s.content_off = d_content_off; s.spans = d_spans; s.info = d_info;
+    hipLaunchKernelGGL(cz_seekable_select_kernel, dim3(1), dim3(CZS_THREADS), 0, c->stream, s);
+    CZ_HIP(c, hipGetLastError());
+    CZ_HIP(c, hipMemcpyAsync(info, d_info, sizeof *info, hipMemcpyDeviceToHost, c->stream));
+    CZ_HIP(c, hipStreamSynchronize(c->stream));
+    return info->status;
+}
+
+CZ_EXPORT int cz_seekable_gather_device(cz_context* c, const void* d_decoded, const uint64_t* d_out_off, const uint64_t* d_content_off, uint64_t k,
+                                        const uint64_t* d_range_off, const uint64_t* d_range_len, const cz_seekable_span* d_spans, size_t m,
+                                        void* d_dst, uint64_t dst_bytes) {
+    if (!c || m > CZ_SEEKABLE_MAX_FRAMES) return CZ_E_INVALID_ARG;
+    if (m == 0 || dst_bytes == 0) return CZ_OK;
+    if (!d_decoded || !d_out_off || !d_content_off || !k || !d_range_off || !d_range_len || !d_spans || !d_dst) return CZ_E_INVALID_ARG;
+    CZ_HIP(c, hipSetDevice(c->device));
+    /* a persistent grid over the tiles of the destination: as many workgroups as the device holds, no more than there are tiles */
+    if (!c->seek_read_grid) {
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, cz_seekable_ranges_kernel, CZS_THREADS, 0) != hipSuccess || occ <= 0) occ = 1;
+        c->seek_read_grid = c->num_cu * occ;
+    }
+    cz_seekable_ranges_args a; memset(&a, 0, sizeof a);
+    a.decoded = (const uint8_t*)d_decoded; a.out_off = (const unsigned long long*)d_out_off; a.content_off = (const unsigned long long*)d_content_off;
+    a.range_off = d_range_off; a.range_len = d_range_len; a.spans = d_spans; a.m = (uint32_t)m; a.dst = (uint8_t*)d_dst; a.dst_bytes = dst_bytes;
+    const uint64_t tiles = (dst_bytes + 15 + 16ull * CZS_TILE_VECS) / (16ull * CZS_TILE_VECS);
+    const unsigned grid = tiles < (uint64_t)c->seek_read_grid ? (unsigned)tiles : (unsigned)c->seek_read_grid;
+    hipLaunchKernelGGL(cz_seekable_ranges_kernel, dim3(grid), dim3(CZS_THREADS), 0, c->stream, a);
+    CZ_HIP(c, hipGetLastError());
+    return CZ_OK;
 }
 
 /* ------------------------------------------------------------------ several devices */

@@ -667,6 +667,77 @@ int cz_seekable_open_host(const void* stream, uint64_t stream_len, uint64_t firs
                           uint64_t* in_off, uint64_t* in_len, uint64_t* out_off, uint64_t* out_cap, uint32_t* checksum,
                           cz_seekable_info* info);
 
+/* ---- byte ranges out of a seekable stream ----
+ * "Content" is the frames' decompressed bytes in frame order, content_bytes of them; a range is (offset, length) in content
+ * coordinates.  Reading m ranges is: an index of the stream (once), a locate (which frames hold a requested byte, and where each
+ * range lies in their decode output), ONE cz_decode_batch_device of those k frames, and a gather of the ranges out of the decoded
+ * frames into one destination, the ranges back to back.
+ *
+ * The index validates the table exactly as cz_seekable_open_device does (the same kernel; the same *info, with detail 0; on
+ * CZ_E_SEEK_TABLE *out is NULL) and keeps in HBM the 64-bit scans of both size columns, the checksums and a per-frame scratch.
+ * `info` is a HOST pointer; the call synchronises the context's stream.  The stream need not outlive the call.  CZ_E_INVALID_ARG for
+ * a NULL ctx / out / info or a NULL stream with a length.  The index belongs to its context and is destroyed before it; calls on one
+ * index are not to run side by side. */
+typedef struct cz_seekable_index cz_seekable_index;
+int  cz_seekable_index_create_device(cz_context* ctx, const void* d_stream, uint64_t stream_len, cz_seekable_index** out, cz_seekable_info* info);
+void cz_seekable_index_destroy(cz_seekable_index* ix);
+typedef struct cz_seekable_span {      /* one per range */
+    uint64_t dst_off;     /* exclusive sum of the ranges' lengths, in range order: where its bytes go in the gather's destination */
+    uint64_t src_off;     /* where its first byte lies in the decode output: out_off[sel_first] + (offset - content_off[sel_first]); 0 for an empty range */
+    uint32_t sel_first;   /* index, among the selected frames, of the frame holding its first byte; 0 for an empty range */
+    uint32_t sel_count;   /* selected frames it touches; 0 for an empty range */
+} cz_seekable_span;                    /* 24 bytes */
+typedef struct cz_seekable_read_info { /* 64 bytes */
+    int32_t  status;        /* CZ_OK | CZ_E_INVALID_ARG | CZ_E_OUTPUT_TOO_SMALL (cz_seekable_locate_host also: CZ_E_SEEK_TABLE) */
+    uint32_t reason;        /* device: reserved, written as 0 (the table was validated when the index was built); host: the table's defect */
+    uint64_t frames, content_bytes;   /* of the table */
+    uint64_t selected;      /* k: frames that hold at least one requested byte */
+    uint64_t out_bytes;     /* decode output the k frames need at out_align: last out_off + last out_cap, 0 for k = 0 */
+    uint64_t dst_bytes;     /* sum of the ranges' lengths */
+    uint64_t detail;        /* a range outside the content: the lowest such index */
+    uint32_t has_checksums, reserved;
+} cz_seekable_read_info;
+/* The selected frames are the union, over the m ranges (DEVICE arrays; they may overlap, repeat and come in any order), of the
+ * frames with Decompressed_Size > 0 that hold a byte of the range, each once, in ascending frame number; an empty range selects
+ * nothing and an empty frame is never selected.  Per selected frame s (DEVICE arrays of frames_cap entries, any of them NULL):
+ * d_frame[s] its frame number, d_in_off / d_in_len / d_out_cap as cz_seekable_open_device gives them for that frame, d_out_off the
+ * exclusive sum of the selected frames' sizes each rounded up to out_align, d_checksum[s] the table's checksum or 0,
+ * d_content_off[s] the frame's first byte in content coordinates.  The first five go into cz_decode_batch_device unchanged, with
+ * n = k.  d_spans (m entries, may be NULL): see cz_seekable_span; the selected frames of one range are consecutive.  With all eight
+ * pointers NULL the call only fills *info (the sizing call).  `info` is a HOST pointer; the call synchronises and returns
+ * info->status.  On any error no array is written and info carries the table's fields:
+ *   CZ_E_INVALID_ARG       out_align not a power of two from 1 to 4096, a NULL ix / info, m above CZ_SEEKABLE_MAX_FRAMES, NULL
+ *                          range arrays with m > 0 (decided on the host, nothing launched); a range with offset > content_bytes
+ *                          or length > content_bytes - offset (decided on the device; detail = the lowest such index)
+ *   CZ_E_OUTPUT_TOO_SMALL  k > frames_cap while a per-frame array is given; selected, out_bytes and dst_bytes still report
+ * It reads the index, never the table again: O(m log n) for the ranges and passes over n 32-bit words for the selection.  The
+ * results depend on the table, the ranges, out_align and frames_cap alone; the index's scratch is clean again when it returns. */
+int cz_seekable_locate_device(cz_seekable_index* ix, const uint64_t* d_range_off, const uint64_t* d_range_len, size_t m,
+                              uint32_t out_align, uint64_t frames_cap,
+                              uint32_t* d_frame, uint64_t* d_in_off, uint64_t* d_in_len, uint64_t* d_out_off, uint64_t* d_out_cap,
+                              uint32_t* d_checksum, uint64_t* d_content_off, cz_seekable_span* d_spans,
+                              cz_seekable_read_info* info);
+/* Copies range j's bytes out of the decoded frames (d_decoded + d_out_off[s]: what cz_decode_batch_device wrote for the k selected
+ * frames) to d_dst + d_spans[j].dst_off: the destination is the ranges back to back, dst_bytes = info->dst_bytes of the locate.
+ * All pointers are DEVICE pointers.  Asynchronous on the context's stream and never synchronises: it can sit directly behind the
+ * decode launch.  No load leaves the bytes of a selected frame that a range asks for; no store leaves [0, dst_bytes), wherever
+ * d_dst points.  m = 0 or dst_bytes = 0 launches nothing.  CZ_E_INVALID_ARG for a NULL ctx, m above CZ_SEEKABLE_MAX_FRAMES, or, with
+ * bytes to copy, a NULL pointer or k = 0.  The arrays must be those of one locate: nothing here is checked on the device. */
+int cz_seekable_gather_device(cz_context* ctx, const void* d_decoded, const uint64_t* d_out_off, const uint64_t* d_content_off, uint64_t k,
+                              const uint64_t* d_range_off, const uint64_t* d_range_len, const cz_seekable_span* d_spans, size_t m,
+                              void* d_dst, uint64_t dst_bytes);
+/* The same on the CPU with HOST buffers and arrays (csrc/czstd_seekable_read_host.h, plain C++): the second implementation, which the
+ * kernels are held to field for field and byte for byte.  cz_seekable_locate_host is stateless: it parses the table through
+ * cz_seekable_open_host's validation each time (a damaged table: CZ_E_SEEK_TABLE with info->reason, every other field 0).
+ * cz_seekable_gather_host also returns CZ_E_INVALID_ARG for a span that leaves [0, dst_bytes). */
+int cz_seekable_locate_host(const void* stream, uint64_t stream_len, const uint64_t* range_off, const uint64_t* range_len, size_t m,
+                            uint32_t out_align, uint64_t frames_cap,
+                            uint32_t* frame, uint64_t* in_off, uint64_t* in_len, uint64_t* out_off, uint64_t* out_cap,
+                            uint32_t* checksum, uint64_t* content_off, cz_seekable_span* spans, cz_seekable_read_info* info);
+int cz_seekable_gather_host(const void* decoded, const uint64_t* out_off, const uint64_t* content_off, uint64_t k,
+                            const uint64_t* range_off, const uint64_t* range_len, const cz_seekable_span* spans, size_t m,
+                            void* dst, uint64_t dst_bytes);
+
 #ifdef __cplusplus
 }
 #endif
