@@ -8,7 +8,8 @@ Python here is a thin mirror over the C ABI (include/cairo_zstd_amd.h, libcairo_
   * compress / compress_batch_host / Context.compress_batch_device : batched compression on the device (split=True: a large
     buffer on many workgroups, still one frame; fse_tables=True: per-block FSE tables for the sequences; fast=True: the fast
     level, 32 KiB blocks that stand alone, one wave each; records=True: the records level, one wave per buffer of at most 32 KiB;
-    fast_split=True: the fast level's frames with the 128 KiB groups of one buffer on many workgroups)
+    fast_split=True: the fast level's frames with the 128 KiB groups of one buffer on many workgroups; high=True: the high-ratio
+    level, two match tables, repeat-offset matches and a lazy parse)
   * compress_batch_host_dict / Context.compress_batch_dict_device : the same with dictionaries (Context.set_compress_dictionaries;
     records=True: the records level with dictionaries)
   * train_dictionary / Context.train_dictionary_device : a zstd dictionary made from samples on the device
@@ -26,7 +27,7 @@ import weakref
 import numpy as np
 
 from . import status
-from ._lib import (COMPRESS_CHECKSUM, COMPRESS_FAST, COMPRESS_FAST_SPLIT, COMPRESS_RECORDS, COMPRESS_FSE_TABLES, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, COMPRESS_SPLIT, SEEKABLE_CHECKSUMS, SEEKABLE_INFO_DTYPE, SEEKABLE_READ_INFO_DTYPE, SEEKABLE_SPAN_DTYPE, TRAIN_MIN_CAPACITY, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
+from ._lib import (COMPRESS_CHECKSUM, COMPRESS_FAST, COMPRESS_FAST_SPLIT, COMPRESS_HIGH, COMPRESS_RECORDS, COMPRESS_FSE_TABLES, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, COMPRESS_SPLIT, SEEKABLE_CHECKSUMS, SEEKABLE_INFO_DTYPE, SEEKABLE_READ_INFO_DTYPE, SEEKABLE_SPAN_DTYPE, TRAIN_MIN_CAPACITY, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
                    BlockHeader, FrameHeader, build, lib)
 
 DEBUG_CHAIN_CPP_STEP, DEBUG_NO_HUF1, DEBUG_WX_POISON, DEBUG_EXEC_FIRST, DEBUG_EXEC_LEAVE = 1, 2, 4, 8, 16     # cz_context_set_debug_flags
@@ -36,7 +37,7 @@ __all__ = ["Context", "FrameDecoder", "BlockDecodingStrategy", "decode_batch_hos
            "read_block_header", "graph_replay_available", "RESULT_DTYPE", "RESULT_FINISHED", "RESULT_HAS_CHECKSUM", "RESULT_CHECKSUM_COMPUTED",
            "RESULT_CHECKSUM_MATCH", "status", "CzError", "build", "lib", "compress_bound", "compress_batch_host", "compress",
            "COMPRESS_CHECKSUM", "COMPRESS_RESULT_DTYPE", "compress_batch_host_dict", "COMPRESS_NO_DICT", "COMPRESS_NO_DICT_ID",
-           "COMPRESS_SPLIT", "compress_split_segment", "COMPRESS_FSE_TABLES", "COMPRESS_FAST", "COMPRESS_FAST_SPLIT", "COMPRESS_RECORDS", "compress_record_max", "train_dictionary", "TRAIN_MIN_CAPACITY",
+           "COMPRESS_SPLIT", "compress_split_segment", "COMPRESS_FSE_TABLES", "COMPRESS_FAST", "COMPRESS_FAST_SPLIT", "COMPRESS_HIGH", "COMPRESS_RECORDS", "compress_record_max", "train_dictionary", "TRAIN_MIN_CAPACITY",
            "SEEKABLE_CHECKSUMS", "SEEKABLE_INFO_DTYPE", "seekable_bound", "pack_seekable", "open_seekable", "decode_seekable",
            "SEEKABLE_READ_INFO_DTYPE", "SEEKABLE_SPAN_DTYPE", "SeekableIndex", "locate_seekable", "read_seekable"]
 
@@ -290,7 +291,7 @@ class Context:
 
     def compress_batch_device(self, in_base: int, in_off: int, in_len: int, n: int, out_base: int, out_off: int,
                               out_cap: int, results: int, checksum: bool = False, split: bool = False, fse_tables: bool = False,
-                              fast: bool = False, records: bool = False, fast_split: bool = False):
+                              fast: bool = False, records: bool = False, fast_split: bool = False, high: bool = False):
         """cz_compress_batch_device.  All arguments are raw DEVICE pointers (tensor.data_ptr()); `results` holds n
         COMPRESS_RESULT_DTYPE records.  Asynchronous on the context's stream, like decode_batch_device.  split=True
         (COMPRESS_SPLIT): inputs longer than compress_split_segment() are compressed by several workgroups, still one frame each.
@@ -299,15 +300,16 @@ class Context:
         records=True (COMPRESS_RECORDS): the records level, one wave per input of at most compress_record_max() bytes; not with
         split, fse_tables or fast.
         fast_split=True (COMPRESS_FAST_SPLIT): the fast level's frames, byte for byte, with the 128 KiB groups of one input on many
-        workgroups; with checksum alone."""
+        workgroups; with checksum alone.
+        high=True (COMPRESS_HIGH): the high-ratio level, the COMPRESS_FSE_TABLES frame with better sequences; with checksum alone."""
         st = lib().cz_compress_batch_device(self._h, in_base, in_off, in_len, n, out_base, out_off, out_cap,
-                                            _compress_flags(checksum, split, fse_tables, fast, records, fast_split), results)
+                                            _compress_flags(checksum, split, fse_tables, fast, records, fast_split, high), results)
         if st:
             raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
 
     def compress_batch_host(self, in_base, in_off, in_len, out_off, out_cap, out: np.ndarray, checksum: bool = False,
                             split: bool = False, fse_tables: bool = False, fast: bool = False, records: bool = False,
-                            fast_split: bool = False):
+                            fast_split: bool = False, high: bool = False):
         """cz_compress_batch_host: host buffers in, `out` (uint8, written in place) out.  Returns the result records."""
         in_base = _as_u8(in_base)
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
@@ -319,7 +321,7 @@ class Context:
         res = np.zeros(n, dtype=COMPRESS_RESULT_DTYPE)
         st = lib().cz_compress_batch_host(self._h, in_base.ctypes.data if in_base.size else None, in_base.size, in_off.ctypes.data,
                                           in_len.ctypes.data, n, out.ctypes.data, out.size, out_off.ctypes.data, out_cap.ctypes.data,
-                                          _compress_flags(checksum, split, fse_tables, fast, records, fast_split), res.ctypes.data)
+                                          _compress_flags(checksum, split, fse_tables, fast, records, fast_split, high), res.ctypes.data)
         if st:
             raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
         return res
@@ -658,13 +660,16 @@ def read_seekable(stream_or_index, ctx: Context, ranges, verify: bool = False, s
             ix.close()
 
 
-def _compress_flags(checksum, split, fse_tables, fast=False, records=False, fast_split=False) -> int:
+def _compress_flags(checksum, split, fse_tables, fast=False, records=False, fast_split=False, high=False) -> int:
+    if high and (split or fse_tables or fast or records or fast_split):
+        raise CzError(status.CZ_E_INVALID_ARG, "high goes with checksum alone: not with split, fse_tables, fast, records or fast_split")
     if fast_split and (split or fse_tables or fast or records):
         raise CzError(status.CZ_E_INVALID_ARG, "fast_split goes with checksum alone: not with split, fse_tables, fast or records")
     if records and (split or fse_tables or fast):
         raise CzError(status.CZ_E_INVALID_ARG, "records goes with checksum alone: not with split, fse_tables or fast")
     return ((COMPRESS_CHECKSUM if checksum else 0) | (COMPRESS_SPLIT if split else 0) | (COMPRESS_FSE_TABLES if fse_tables else 0)
-            | (COMPRESS_FAST if fast else 0) | (COMPRESS_RECORDS if records else 0) | (COMPRESS_FAST_SPLIT if fast_split else 0))
+            | (COMPRESS_FAST if fast else 0) | (COMPRESS_RECORDS if records else 0) | (COMPRESS_FAST_SPLIT if fast_split else 0)
+            | (COMPRESS_HIGH if high else 0))
 
 
 def compress_bound(n: int) -> int:
@@ -683,14 +688,15 @@ def compress_record_max() -> int:
 
 
 def compress_batch_host(buffers, ctx: Context, checksum: bool = False, split: bool = False, fse_tables: bool = False,
-                        fast: bool = False, records: bool = False, fast_split: bool = False):
+                        fast: bool = False, records: bool = False, fast_split: bool = False, high: bool = False):
     """Compresses every buffer into one zstd frame, in one launch: list of (result record, frame bytes).  split=True: buffers
     longer than compress_split_segment() are compressed by several workgroups side by side (COMPRESS_SPLIT).  fse_tables=True:
     the sequences of a block take FSE tables made for that block where they make it smaller (COMPRESS_FSE_TABLES).  fast=True:
     the fast level (COMPRESS_FAST), which the library refuses together with split or fse_tables.  records=True: the records level
     (COMPRESS_RECORDS) for buffers of at most compress_record_max() bytes, one wave each; not with the three before it.  fast_split=True: the fast
     level's frames, byte for byte, with the 128 KiB groups of one buffer on many workgroups (COMPRESS_FAST_SPLIT), for few, large
-    buffers; with checksum alone."""
+    buffers; with checksum alone.  high=True: the high-ratio level (COMPRESS_HIGH): the frame of fse_tables=True with sequences from
+    two match tables, repeat-offset matches and a lazy parse; with checksum alone."""
     lens = np.array([len(b) for b in buffers], dtype=np.uint64)
     in_off = np.zeros(len(buffers), dtype=np.uint64)
     if len(buffers) > 1:
@@ -702,7 +708,7 @@ def compress_batch_host(buffers, ctx: Context, checksum: bool = False, split: bo
         out_off[1:] = np.cumsum(caps[:-1])
     out = np.zeros(max(int(caps.sum()), 1), dtype=np.uint8)
     res = ctx.compress_batch_host(in_base, in_off, lens, out_off, caps, out, checksum=checksum, split=split, fse_tables=fse_tables,
-                                  fast=fast, records=records, fast_split=fast_split)
+                                  fast=fast, records=records, fast_split=fast_split, high=high)
     return [(res[i], out[int(out_off[i]): int(out_off[i]) + int(res[i]["bytes_written"])].tobytes()) for i in range(len(buffers))]
 
 
@@ -727,12 +733,12 @@ def compress_batch_host_dict(buffers, dict_index, ctx: Context, checksum: bool =
 
 
 def compress(data, ctx: Context, checksum: bool = False, split: bool = False, fse_tables: bool = False, fast: bool = False,
-             records: bool = False, fast_split: bool = False) -> bytes:
+             records: bool = False, fast_split: bool = False, high: bool = False) -> bytes:
     """One buffer -> one zstd frame (through the batched kernel; split=True: on many workgroups when it is large; fse_tables=True:
     per-block FSE tables for the sequences; fast=True: the fast level; records=True: the records level; fast_split=True: the fast
-    level on many workgroups when the buffer is large)."""
+    level on many workgroups when the buffer is large; high=True: the high-ratio level)."""
     (r, frame), = compress_batch_host([data], ctx, checksum=checksum, split=split, fse_tables=fse_tables, fast=fast, records=records,
-                                      fast_split=fast_split)
+                                      fast_split=fast_split, high=high)
     if int(r["status"]):
         raise CzError(int(r["status"]), "cz_compress_batch_host")
     return frame

@@ -28,6 +28,8 @@
  * cz_compress_frames_fse_kernel is cz_compress_frames_kernel, cz_compress_segments_fse_kernel is cz_compress_segments_kernel (same
  * plan kernel, same chain word, same progress argument), each around czf_block.  They have copies of their own of everything:
  * the kernels of czstd_enc.hip and czstd_encsplit.hip compile as they did without this file.  Included behind czstd_encsplit.hip.
+ * USER (czf_sequences, czf_predefined and what they call): as for cze_sequences, a copy of its own for a kernel of a later file
+ * (czstd_enchigh.hip: 1), so that a second caller changes no inlining decision in the two kernels here.
  */
 #define CZF_LL 0u
 #define CZF_OF 1u
@@ -60,7 +62,7 @@ __device__ static inline uint32_t czf_maxlog(uint32_t f) { return f == CZF_OF ? 
 __device__ static inline uint32_t czf_states(int v) { return v == -1 ? 1u : (uint32_t)v; }
 
 /* one lane: spreads the symbols as the decoder does (RFC 8878 §4.1.1) */
-__device__ static void czf_spread(const int16_t* norm, uint32_t nsym, uint32_t log, uint8_t* sym) {
+template <int USER = 0> __device__ static void czf_spread(const int16_t* norm, uint32_t nsym, uint32_t log, uint8_t* sym) {
     const uint32_t size = 1u << log, mask = size - 1;
     uint32_t high = size - 1;
     for (uint32_t s = 0; s < nsym; s++) if (norm[s] == -1) sym[high--] = (uint8_t)s;
@@ -70,7 +72,7 @@ __device__ static void czf_spread(const int16_t* norm, uint32_t nsym, uint32_t l
         for (int i = 0; i < norm[s]; i++) { sym[pos] = (uint8_t)s; do pos = (pos + step) & mask; while (pos > high); }
 }
 /* one thread per symbol: deltaFindState and deltaNbBits */
-__device__ static void czf_symbol(uint32_t tb, const int16_t* norm, uint32_t s, uint32_t log) {
+template <int USER = 0> __device__ static void czf_symbol(uint32_t tb, const int16_t* norm, uint32_t s, uint32_t log) {
     const uint32_t n = czf_states(norm[s]);
     uint32_t c0 = 0;
     for (uint32_t v = 0; v < s; v++) c0 += czf_states(norm[v]);
@@ -80,7 +82,7 @@ __device__ static void czf_symbol(uint32_t tb, const int16_t* norm, uint32_t s, 
     czf.dnb[tb][s] = (mbo << 16) - (n << mbo);
 }
 /* one thread per state u: the states of a symbol in increasing order; a stream may start in the lowest */
-__device__ static void czf_state(uint32_t tb, const int16_t* norm, const uint8_t* sym, uint32_t u) {
+template <int USER = 0> __device__ static void czf_state(uint32_t tb, const int16_t* norm, const uint8_t* sym, uint32_t u) {
     const uint32_t s = sym[u];
     uint32_t rank = 0;
     for (uint32_t v = 0; v < u; v++) rank += sym[v] == s;
@@ -88,20 +90,20 @@ __device__ static void czf_state(uint32_t tb, const int16_t* norm, const uint8_t
     if (rank == 0) czf.first[tb][s] = (uint16_t)u;
 }
 /* all threads: tables 2 f + own of the fields in `active` from czf.norm[f] and czf.log[2 f + own] */
-__device__ static void czf_build(uint32_t own, uint32_t active) {
+template <int USER = 0> __device__ static void czf_build(uint32_t own, uint32_t active) {
     const uint32_t t = threadIdx.x;
-    if (t < 3) { if ((active >> t) & 1u) czf_spread(czf.norm[t], czf_nsym(t), czf.log[2 * t + own], czf.spread[t]); }
+    if (t < 3) { if ((active >> t) & 1u) czf_spread<USER>(czf.norm[t], czf_nsym(t), czf.log[2 * t + own], czf.spread[t]); }
     else if (t >= 64) {
         const uint32_t f = (t - 64) >> 6, s = (t - 64) & 63u;
-        if (((active >> f) & 1u) && s < czf_nsym(f)) czf_symbol(2 * f + own, czf.norm[f], s, czf.log[2 * f + own]);
+        if (((active >> f) & 1u) && s < czf_nsym(f)) czf_symbol<USER>(2 * f + own, czf.norm[f], s, czf.log[2 * f + own]);
     }
     __syncthreads();
     for (uint32_t f = 0; f < 3; f++) if ((active >> f) & 1u)
-        for (uint32_t u = t; u < (1u << czf.log[2 * f + own]); u += CZE_THREADS) czf_state(2 * f + own, czf.norm[f], czf.spread[f], u);
+        for (uint32_t u = t; u < (1u << czf.log[2 * f + own]); u += CZE_THREADS) czf_state<USER>(2 * f + own, czf.norm[f], czf.spread[f], u);
     __syncthreads();
 }
 /* all threads, once per kernel: the Predefined tables (RFC 8878 §3.1.1.3.2.2) */
-__device__ static void czf_predefined() {
+template <int USER = 0> __device__ static void czf_predefined() {
     const uint32_t t = threadIdx.x;
     if (t < 64) {
         czf.norm[CZF_LL][t] = t < 36 ? CZ_LL_DEFAULT[t] : 0;
@@ -110,12 +112,12 @@ __device__ static void czf_predefined() {
     }
     if (t == 0) { czf.log[2 * CZF_LL] = 6; czf.log[2 * CZF_OF] = 5; czf.log[2 * CZF_ML] = 6; }
     __syncthreads();
-    czf_build(0u, 7u);
+    czf_build<USER>(0u, 7u);
 }
 
 /* one lane: field f of a block of n sequences from czf.hist[f] — the used codes, and for two or more the accuracy log, the
    normalised counts and the table description (the forward bit stream of RFC 8878 §4.1.1) */
-__device__ static void czf_normalise(uint32_t f, uint32_t n) {
+template <int USER = 0> __device__ static void czf_normalise(uint32_t f, uint32_t n) {
     const uint32_t nsym = czf_nsym(f);
     uint32_t used = 0, maxs = 0, big = 0;
     for (uint32_t s = 0; s < nsym; s++) {
@@ -176,7 +178,7 @@ __device__ static inline void czf_or(uint32_t* W, uint32_t o, uint64_t v, uint32
 
 /* all threads: the sequences section of n sequences at out[0, lim); returns its length, or lim + 1 when it does not fit (every
    thread).  W: a zeroable word buffer of at least lim + 16 bytes; fscr: the CZF_SCR_* scratch. */
-__device__ static uint32_t czf_sequences(const CzeSeq* sq, uint32_t n, uint32_t nlit, uint8_t* out, uint32_t lim, uint32_t* W, uint8_t* fscr) {
+template <int USER = 0> __device__ static uint32_t czf_sequences(const CzeSeq* sq, uint32_t n, uint32_t nlit, uint8_t* out, uint32_t lim, uint32_t* W, uint8_t* fscr) {
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
     if (n == 0) { if (t == 0 && lim >= 1) out[0] = 0; return lim >= 1 ? 1u : lim + 1; }
     uint8_t* code = fscr + CZF_SCR_CODE;
@@ -196,10 +198,10 @@ __device__ static uint32_t czf_sequences(const CzeSeq* sq, uint32_t n, uint32_t 
     uint32_t extra;
     (void)cze_wg_scan(xb, &extra);
     /* the block's own tables */
-    if (lane == 0 && wave < 3) czf_normalise(wave, n);
+    if (lane == 0 && wave < 3) czf_normalise<USER>(wave, n);
     __syncthreads();
     const uint32_t active = (czf.used[0] >= 2 ? 1u : 0u) | (czf.used[1] >= 2 ? 2u : 0u) | (czf.used[2] >= 2 ? 4u : 0u);
-    if (active) czf_build(1u, active);
+    if (active) czf_build<USER>(1u, active);
     /* the six chains: state after sequence k from the state after k + 1 and the code of k */
     if (t < 6 && (!(t & 1u) || ((active >> (t >> 1)) & 1u))) {
         const uint32_t tb = t, size = 1u << czf.log[tb];

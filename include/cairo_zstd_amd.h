@@ -432,7 +432,8 @@ int  cz_frame_decoder_decode_from_to(cz_frame_decoder* fd, const uint8_t* src, s
 /* ------------------------------------------------------------- compression */
 /*
  * Batched compression: n independent buffers become n standard zstd frames in one launch (cz_compress_frames_kernel,
- * DESIGN.md §10).  Any conforming decoder reads them.  One level: greedy matches from a hash table of 4-byte keys.
+ * DESIGN.md §10).  Any conforming decoder reads them.  The levels but one take greedy matches
+ * from a hash table of 4-byte keys; CZ_COMPRESS_HIGH adds a second table, repeat-offset matches and a lazy parse.
  * Frame format: magic; Frame_Content_Size always written; Single_Segment when the input is at most 1 MiB, otherwise a
  * 1 MiB window (no offset exceeds it); no Dictionary_ID.  Blocks of at most 128 KiB, each Raw, RLE or Compressed,
  * whichever is smallest (an empty input: one empty last Raw block).  Literals Raw, RLE or Huffman (one stream below
@@ -520,6 +521,23 @@ uint64_t cz_compress_record_max(void);   /* 32768: the largest input CZ_COMPRESS
  * CZ_E_INVALID_ARG together with any other flag but the checksum and in cz_compress_batch_dict_*.
  */
 #define CZ_COMPRESS_FAST_SPLIT 128u
+/*
+ * CZ_COMPRESS_HIGH (cz_compress_batch_device / _host only, alone or with CZ_COMPRESS_CHECKSUM): the high-ratio
+ * level.  Everything about the frame but the choice of sequences is the CZ_COMPRESS_FSE_TABLES frame, which the level implies: the
+ * same header, blocks of at most 128 KiB each Raw, RLE or Compressed, the same literals, and per block and field Predefined, RLE
+ * or FSE_Compressed mode by exact size; Repeat_Mode and Treeless literals are never written; cz_compress_bound holds,
+ * CZ_E_OUTPUT_TOO_SMALL ends the frame at a block boundary with nothing past bytes_written touched, and an input of 0xFFF00000 bytes
+ * or more is CZ_E_INVALID_ARG.  An input without any match (empty, below 16 bytes, an RLE block, random bytes) comes out byte for
+ * byte as with CZ_COMPRESS_FSE_TABLES.  The sequences come from two candidates per position (the 4-byte table and a second table
+ * of 8-byte keys that keeps long matches), from the offset history, which is tried as a match of its own and written with all six
+ * repeat-offset cases of the format (an offset the history holds in a usable place is never written in full), and from a lazy
+ * parse that gives up a short match for a longer one at one of the next two positions.  Offsets stay within 1 MiB.  The bytes
+ * depend on the input and the flags alone, never on the batch, the grid or timing.  The result flags carry the bit whenever it was
+ * requested.  The value is 256: 8 stays an unknown bit.  CZ_E_INVALID_ARG together with CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES,
+ * CZ_COMPRESS_FAST, CZ_COMPRESS_RECORDS or CZ_COMPRESS_FAST_SPLIT and in cz_compress_batch_dict_*: the split and dictionary forms
+ * of the level are left for later.
+ */
+#define CZ_COMPRESS_HIGH 256u
 /* One per buffer, written by the device. */
 typedef struct cz_compress_result {
     int32_t  status;            /* CZ_OK | CZ_E_OUTPUT_TOO_SMALL | CZ_E_INVALID_ARG (an input of 4 GiB - 1 MiB or more) | CZ_E_WAIT_EXPIRED */
@@ -533,8 +551,8 @@ typedef struct cz_compress_result {
  * (results too); asynchronous on the context stream; no alignment required.  A frame that fails leaves its neighbours and
  * every byte of its own region past bytes_written untouched.  out_cap[i] = cz_compress_bound(in_len[i]) always suffices.
  * flags: CZ_COMPRESS_CHECKSUM, CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES, CZ_COMPRESS_FAST (not with the two before it),
- * CZ_COMPRESS_RECORDS (not with the three before it), CZ_COMPRESS_FAST_SPLIT (with the checksum only); any other bit is
- * CZ_E_INVALID_ARG. */
+ * CZ_COMPRESS_RECORDS (not with the three before it), CZ_COMPRESS_FAST_SPLIT (with the checksum only), CZ_COMPRESS_HIGH (with the
+ * checksum only); any other bit is CZ_E_INVALID_ARG. */
 int cz_compress_batch_device(cz_context* ctx, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                              void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                              cz_compress_result* d_results);

@@ -12,6 +12,8 @@ batch compressed as a frame of its own, the floor the choice of segment and over
 or overlap (make -C cairo_zstd_amd/csrc exp NAME=s2w128 EXPFLAGS="-DCZE_SEG_BLOCKS=2u -DCZE_OVERLAP=131072u") are picked with
 CAIRO_ZSTD_AMD_LIB; --tag goes into every row to tell them apart.
 
+--high measures CZ_COMPRESS_HIGH next to CZ_COMPRESS_FSE_TABLES and libzstd levels 1, 3 and 6 (DESIGN.md §10.8;
+profiles/compress/high_bench.json).
 --fse-tables measures CZ_COMPRESS_FSE_TABLES: every batch unsplit and split, each without and with the flag in
 the same session, and the frame bytes of the 69 corpus originals without and with it; --out defaults to
 profiles/compress/fse_bench.json."""
@@ -41,7 +43,7 @@ def tiled(n, size, seed):
     return [pool[int(s):int(s) + size] for s in starts]
 
 
-def device_run(cz, ctx, stream, bufs, runs, split=False, fse=False):
+def device_run(cz, ctx, stream, bufs, runs, split=False, fse=False, high=False):
     import torch
     dev = torch.device("cuda:0")
     lens = np.array([len(b) for b in bufs], dtype=np.uint64)
@@ -61,7 +63,7 @@ def device_run(cz, ctx, stream, bufs, runs, split=False, fse=False):
         e0.record(stream)
         ctx.compress_batch_device(d_in.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), len(bufs), d_out.data_ptr(),
                                   desc[2].data_ptr(), desc[3].data_ptr(), d_res.data_ptr(), **(dict(split=True) if split else {}),
-                                  **(dict(fse_tables=True) if fse else {}))
+                                  **(dict(fse_tables=True) if fse else {}), **(dict(high=True) if high else {}))
         e1.record(stream)
         e1.synchronize()
         if r:
@@ -71,7 +73,7 @@ def device_run(cz, ctx, stream, bufs, runs, split=False, fse=False):
     return float(np.median(times)), int(res["bytes_written"].sum())
 
 
-def libzstd_run(bufs, threads, runs):
+def libzstd_run(bufs, threads, runs, level=1):
     try:
         z = ctypes.CDLL("libzstd.so.1")
     except OSError:
@@ -84,7 +86,7 @@ def libzstd_run(bufs, threads, runs):
     outs = [ctypes.create_string_buffer(z.ZSTD_compressBound(len(b))) for b in bufs]
 
     def one(i):
-        return z.ZSTD_compress(outs[i], len(outs[i]), bufs[i], len(bufs[i]), 1)     # ctypes drops the GIL around the call
+        return z.ZSTD_compress(outs[i], len(outs[i]), bufs[i], len(bufs[i]), level)     # ctypes drops the GIL around the call
     best, total = None, 0
     with ThreadPoolExecutor(threads) as ex:
         for _ in range(runs):
@@ -96,6 +98,41 @@ def libzstd_run(bufs, threads, runs):
     return best * 1e3, total, z.ZSTD_versionNumber()
 
 
+def high_bench(args, cz, ctx, stream, device):
+    """CZ_COMPRESS_FSE_TABLES and CZ_COMPRESS_HIGH in one session: frame bytes of the corpus originals, kernel time (median of
+    --runs after a warm-up) and ratio on 10 000 x 128 KiB and 64 x 2 MiB, libzstd levels 1, 3 and 6 on --threads CPUs."""
+    out = args.out or os.path.join(ROOT, "profiles", "compress", "high_bench.json")
+    d = os.path.join(ROOT, "tests", "golden", "decode_corpus")
+    originals = [open(os.path.join(d, n), "rb").read() for n in sorted(os.listdir(d)) if not n.endswith(".zst")]
+    row = dict(batch="corpus originals", count=len(originals), input_bytes=sum(map(len, originals)))
+    row["frame_bytes_fse_tables"] = sum(len(fr) for _, fr in cz.compress_batch_host(originals, ctx, fse_tables=True))
+    row["frame_bytes_high"] = sum(len(fr) for _, fr in cz.compress_batch_host(originals, ctx, high=True))
+    for level in (() if args.no_libzstd else (1, 3, 6)):
+        cpu = libzstd_run(originals, args.threads, 1, level)
+        if cpu:
+            row[f"libzstd_{level}_frame_bytes"] = cpu[1]
+    rows = [row]
+    print(json.dumps(row), flush=True)
+    for name, n, size in (("10000x128KiB", 10000, 128 << 10), ("64x2MiB", 64, 2 << 20)):
+        bufs = tiled(n, size, seed=1)
+        nbytes = n * size
+        row = dict(batch=name, input_bytes=nbytes, device=device)
+        for key, kw in (("fse_tables", dict(fse=True)), ("high", dict(high=True)), ("fse_tables_again", dict(fse=True))):
+            ms, written = device_run(cz, ctx, stream, bufs, args.runs, **kw)
+            row[key] = dict(device_ms=round(ms, 3), device_gbps=round(nbytes / ms / 1e6, 2), device_ratio=round(nbytes / written, 4), frame_bytes=written)
+        for level in (() if args.no_libzstd else (1, 3, 6)):
+            cpu = libzstd_run(bufs, args.threads, args.runs, level)
+            if cpu:
+                row[f"libzstd_{level}"] = dict(threads=args.threads, ms=round(cpu[0], 3), gbps=round(nbytes / cpu[0] / 1e6, 2), ratio=round(nbytes / cpu[1], 4))
+        if args.tag:
+            row["tag"] = args.tag
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -104,6 +141,7 @@ def main():
     ap.add_argument("--split", action="store_true", help="compress with CZ_COMPRESS_SPLIT")
     ap.add_argument("--pieces", action="store_true", help="also: the 64 x 2 MiB batch as 1 024 frames of 128 KiB (frame bytes)")
     ap.add_argument("--fse-tables", action="store_true", help="measure CZ_COMPRESS_FSE_TABLES next to the same launches without it")
+    ap.add_argument("--high", action="store_true", help="measure CZ_COMPRESS_HIGH next to CZ_COMPRESS_FSE_TABLES, and libzstd levels 1, 3 and 6")
     ap.add_argument("--no-libzstd", action="store_true")
     ap.add_argument("--tag", default=None, help="free text copied into every row")
     args = ap.parse_args()
@@ -121,6 +159,10 @@ def main():
             row[key] = sum(len(fr) for _, fr in cz.compress_batch_host(originals, ctx, fse_tables=fse))
         print(json.dumps(row), flush=True)
         rows.append(row)
+    if args.high:
+        high_bench(args, cz, ctx, stream, torch.cuda.get_device_name(0))
+        ctx.close()
+        return
     variants = [(s, f) for s in (False, True) for f in (False, True)] if args.fse_tables else [(args.split, False)]
     for name, n, size in (("10000x128KiB", 10000, 128 << 10), ("64x2MiB", 64, 2 << 20), ("1x16MiB", 1, 16 << 20)):
         bufs = tiled(n, size, seed=1)
