@@ -9,7 +9,8 @@ Python here is a thin mirror over the C ABI (include/cairo_zstd_amd.h, libcairo_
     buffer on many workgroups, still one frame; fse_tables=True: per-block FSE tables for the sequences; fast=True: the fast
     level, 32 KiB blocks that stand alone, one wave each; records=True: the records level, one wave per buffer of at most 32 KiB;
     fast_split=True: the fast level's frames with the 128 KiB groups of one buffer on many workgroups; high=True: the high-ratio
-    level, two match tables, repeat-offset matches and a lazy parse)
+    level, two match tables, repeat-offset matches and a lazy parse; high_split=True: that level with the segments of one buffer
+    on many workgroups)
   * compress_batch_host_dict / Context.compress_batch_dict_device : the same with dictionaries (Context.set_compress_dictionaries;
     records=True: the records level with dictionaries)
   * train_dictionary / Context.train_dictionary_device : a zstd dictionary made from samples on the device
@@ -27,7 +28,7 @@ import weakref
 import numpy as np
 
 from . import status
-from ._lib import (COMPRESS_CHECKSUM, COMPRESS_FAST, COMPRESS_FAST_SPLIT, COMPRESS_HIGH, COMPRESS_RECORDS, COMPRESS_FSE_TABLES, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, COMPRESS_SPLIT, SEEKABLE_CHECKSUMS, SEEKABLE_INFO_DTYPE, SEEKABLE_READ_INFO_DTYPE, SEEKABLE_SPAN_DTYPE, TRAIN_MIN_CAPACITY, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
+from ._lib import (COMPRESS_CHECKSUM, COMPRESS_FAST, COMPRESS_FAST_SPLIT, COMPRESS_HIGH, COMPRESS_HIGH_SPLIT, COMPRESS_RECORDS, COMPRESS_FSE_TABLES, COMPRESS_NO_DICT, COMPRESS_NO_DICT_ID, COMPRESS_RESULT_DTYPE, COMPRESS_SPLIT, SEEKABLE_CHECKSUMS, SEEKABLE_INFO_DTYPE, SEEKABLE_READ_INFO_DTYPE, SEEKABLE_SPAN_DTYPE, TRAIN_MIN_CAPACITY, RESULT_CHECKSUM_COMPUTED, RESULT_CHECKSUM_MATCH, RESULT_DTYPE, RESULT_FINISHED, RESULT_HAS_CHECKSUM,
                    BlockHeader, FrameHeader, build, lib)
 
 DEBUG_CHAIN_CPP_STEP, DEBUG_NO_HUF1, DEBUG_WX_POISON, DEBUG_EXEC_FIRST, DEBUG_EXEC_LEAVE = 1, 2, 4, 8, 16     # cz_context_set_debug_flags
@@ -37,7 +38,7 @@ __all__ = ["Context", "FrameDecoder", "BlockDecodingStrategy", "decode_batch_hos
            "read_block_header", "graph_replay_available", "RESULT_DTYPE", "RESULT_FINISHED", "RESULT_HAS_CHECKSUM", "RESULT_CHECKSUM_COMPUTED",
            "RESULT_CHECKSUM_MATCH", "status", "CzError", "build", "lib", "compress_bound", "compress_batch_host", "compress",
            "COMPRESS_CHECKSUM", "COMPRESS_RESULT_DTYPE", "compress_batch_host_dict", "COMPRESS_NO_DICT", "COMPRESS_NO_DICT_ID",
-           "COMPRESS_SPLIT", "compress_split_segment", "COMPRESS_FSE_TABLES", "COMPRESS_FAST", "COMPRESS_FAST_SPLIT", "COMPRESS_HIGH", "COMPRESS_RECORDS", "compress_record_max", "train_dictionary", "TRAIN_MIN_CAPACITY",
+           "COMPRESS_SPLIT", "compress_split_segment", "COMPRESS_FSE_TABLES", "COMPRESS_FAST", "COMPRESS_FAST_SPLIT", "COMPRESS_HIGH", "COMPRESS_HIGH_SPLIT", "COMPRESS_RECORDS", "compress_record_max", "train_dictionary", "TRAIN_MIN_CAPACITY",
            "SEEKABLE_CHECKSUMS", "SEEKABLE_INFO_DTYPE", "seekable_bound", "pack_seekable", "open_seekable", "decode_seekable",
            "SEEKABLE_READ_INFO_DTYPE", "SEEKABLE_SPAN_DTYPE", "SeekableIndex", "locate_seekable", "read_seekable"]
 
@@ -291,7 +292,8 @@ class Context:
 
     def compress_batch_device(self, in_base: int, in_off: int, in_len: int, n: int, out_base: int, out_off: int,
                               out_cap: int, results: int, checksum: bool = False, split: bool = False, fse_tables: bool = False,
-                              fast: bool = False, records: bool = False, fast_split: bool = False, high: bool = False):
+                              fast: bool = False, records: bool = False, fast_split: bool = False, high: bool = False,
+                              high_split: bool = False):
         """cz_compress_batch_device.  All arguments are raw DEVICE pointers (tensor.data_ptr()); `results` holds n
         COMPRESS_RESULT_DTYPE records.  Asynchronous on the context's stream, like decode_batch_device.  split=True
         (COMPRESS_SPLIT): inputs longer than compress_split_segment() are compressed by several workgroups, still one frame each.
@@ -301,15 +303,17 @@ class Context:
         split, fse_tables or fast.
         fast_split=True (COMPRESS_FAST_SPLIT): the fast level's frames, byte for byte, with the 128 KiB groups of one input on many
         workgroups; with checksum alone.
-        high=True (COMPRESS_HIGH): the high-ratio level, the COMPRESS_FSE_TABLES frame with better sequences; with checksum alone."""
+        high=True (COMPRESS_HIGH): the high-ratio level, the COMPRESS_FSE_TABLES frame with better sequences; with checksum alone.
+        high_split=True (COMPRESS_HIGH_SPLIT): the high-ratio level with the segments of one input (compress_split_segment() bytes
+        each) on many workgroups, still one frame each; with checksum alone."""
         st = lib().cz_compress_batch_device(self._h, in_base, in_off, in_len, n, out_base, out_off, out_cap,
-                                            _compress_flags(checksum, split, fse_tables, fast, records, fast_split, high), results)
+                                            _compress_flags(checksum, split, fse_tables, fast, records, fast_split, high, high_split), results)
         if st:
             raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
 
     def compress_batch_host(self, in_base, in_off, in_len, out_off, out_cap, out: np.ndarray, checksum: bool = False,
                             split: bool = False, fse_tables: bool = False, fast: bool = False, records: bool = False,
-                            fast_split: bool = False, high: bool = False):
+                            fast_split: bool = False, high: bool = False, high_split: bool = False):
         """cz_compress_batch_host: host buffers in, `out` (uint8, written in place) out.  Returns the result records."""
         in_base = _as_u8(in_base)
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
@@ -321,29 +325,31 @@ class Context:
         res = np.zeros(n, dtype=COMPRESS_RESULT_DTYPE)
         st = lib().cz_compress_batch_host(self._h, in_base.ctypes.data if in_base.size else None, in_base.size, in_off.ctypes.data,
                                           in_len.ctypes.data, n, out.ctypes.data, out.size, out_off.ctypes.data, out_cap.ctypes.data,
-                                          _compress_flags(checksum, split, fse_tables, fast, records, fast_split, high), res.ctypes.data)
+                                          _compress_flags(checksum, split, fse_tables, fast, records, fast_split, high, high_split), res.ctypes.data)
         if st:
             raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
         return res
 
     def compress_batch_dict_device(self, in_base: int, in_off: int, in_len: int, n: int, out_base: int, out_off: int,
                                    out_cap: int, dict_index: int, results: int, checksum: bool = False, dict_id: bool = True,
-                                   records: bool = False, fast_split: bool = False):
+                                   records: bool = False, fast_split: bool = False, high_split: bool = False):
         """cz_compress_batch_dict_device: as compress_batch_device, frame i with dictionary dict_index[i] of
         set_compress_dictionaries (COMPRESS_NO_DICT: none).  dict_index is a DEVICE pointer to n uint32 (0: every frame uses the
         one dictionary set).  dict_id=False omits the Dictionary_ID field.  records=True (COMPRESS_RECORDS): the records level.
-        fast_split=True (COMPRESS_FAST_SPLIT) is refused here, as by the library: that level takes no dictionary."""
+        fast_split=True (COMPRESS_FAST_SPLIT) and high_split=True (COMPRESS_HIGH_SPLIT) are refused here, as by the library: those
+        levels take no dictionary."""
         flags = ((COMPRESS_CHECKSUM if checksum else 0) | (0 if dict_id else COMPRESS_NO_DICT_ID) | (COMPRESS_RECORDS if records else 0)
-                 | (COMPRESS_FAST_SPLIT if fast_split else 0))
+                 | (COMPRESS_FAST_SPLIT if fast_split else 0) | (COMPRESS_HIGH_SPLIT if high_split else 0))
         st = lib().cz_compress_batch_dict_device(self._h, in_base, in_off, in_len, n, out_base, out_off, out_cap, flags,
                                                  dict_index or None, results)
         if st:
             raise CzError(st, f"hip error {lib().cz_context_last_hip_error(self._h)}")
 
     def compress_batch_dict_host(self, in_base, in_off, in_len, out_off, out_cap, out: np.ndarray, dict_index,
-                                 checksum: bool = False, dict_id: bool = True, records: bool = False, fast_split: bool = False):
+                                 checksum: bool = False, dict_id: bool = True, records: bool = False, fast_split: bool = False,
+                                 high_split: bool = False):
         """cz_compress_batch_dict_host: as compress_batch_host, with a dictionary index per buffer (None: every buffer uses the
-        one dictionary set).  records=True (COMPRESS_RECORDS): the records level.  fast_split=True is refused, as by the library.
+        one dictionary set).  records=True (COMPRESS_RECORDS): the records level.  fast_split=True and high_split=True are refused, as by the library.
         Returns the result records."""
         in_base = _as_u8(in_base)
         in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
@@ -355,7 +361,7 @@ class Context:
         n = int(in_off.size)
         res = np.zeros(n, dtype=COMPRESS_RESULT_DTYPE)
         flags = ((COMPRESS_CHECKSUM if checksum else 0) | (0 if dict_id else COMPRESS_NO_DICT_ID) | (COMPRESS_RECORDS if records else 0)
-                 | (COMPRESS_FAST_SPLIT if fast_split else 0))
+                 | (COMPRESS_FAST_SPLIT if fast_split else 0) | (COMPRESS_HIGH_SPLIT if high_split else 0))
         st = lib().cz_compress_batch_dict_host(self._h, in_base.ctypes.data if in_base.size else None, in_base.size, in_off.ctypes.data,
                                                in_len.ctypes.data, n, out.ctypes.data, out.size, out_off.ctypes.data, out_cap.ctypes.data,
                                                flags, None if idx is None else idx.ctypes.data, res.ctypes.data)
@@ -660,7 +666,9 @@ def read_seekable(stream_or_index, ctx: Context, ranges, verify: bool = False, s
             ix.close()
 
 
-def _compress_flags(checksum, split, fse_tables, fast=False, records=False, fast_split=False, high=False) -> int:
+def _compress_flags(checksum, split, fse_tables, fast=False, records=False, fast_split=False, high=False, high_split=False) -> int:
+    if high_split and (split or fse_tables or fast or records or fast_split or high):
+        raise CzError(status.CZ_E_INVALID_ARG, "high_split goes with checksum alone: not with split, fse_tables, fast, records, fast_split or high")
     if high and (split or fse_tables or fast or records or fast_split):
         raise CzError(status.CZ_E_INVALID_ARG, "high goes with checksum alone: not with split, fse_tables, fast, records or fast_split")
     if fast_split and (split or fse_tables or fast or records):
@@ -669,7 +677,7 @@ def _compress_flags(checksum, split, fse_tables, fast=False, records=False, fast
         raise CzError(status.CZ_E_INVALID_ARG, "records goes with checksum alone: not with split, fse_tables or fast")
     return ((COMPRESS_CHECKSUM if checksum else 0) | (COMPRESS_SPLIT if split else 0) | (COMPRESS_FSE_TABLES if fse_tables else 0)
             | (COMPRESS_FAST if fast else 0) | (COMPRESS_RECORDS if records else 0) | (COMPRESS_FAST_SPLIT if fast_split else 0)
-            | (COMPRESS_HIGH if high else 0))
+            | (COMPRESS_HIGH if high else 0) | (COMPRESS_HIGH_SPLIT if high_split else 0))
 
 
 def compress_bound(n: int) -> int:
@@ -688,7 +696,8 @@ def compress_record_max() -> int:
 
 
 def compress_batch_host(buffers, ctx: Context, checksum: bool = False, split: bool = False, fse_tables: bool = False,
-                        fast: bool = False, records: bool = False, fast_split: bool = False, high: bool = False):
+                        fast: bool = False, records: bool = False, fast_split: bool = False, high: bool = False,
+                        high_split: bool = False):
     """Compresses every buffer into one zstd frame, in one launch: list of (result record, frame bytes).  split=True: buffers
     longer than compress_split_segment() are compressed by several workgroups side by side (COMPRESS_SPLIT).  fse_tables=True:
     the sequences of a block take FSE tables made for that block where they make it smaller (COMPRESS_FSE_TABLES).  fast=True:
@@ -696,7 +705,9 @@ def compress_batch_host(buffers, ctx: Context, checksum: bool = False, split: bo
     (COMPRESS_RECORDS) for buffers of at most compress_record_max() bytes, one wave each; not with the three before it.  fast_split=True: the fast
     level's frames, byte for byte, with the 128 KiB groups of one buffer on many workgroups (COMPRESS_FAST_SPLIT), for few, large
     buffers; with checksum alone.  high=True: the high-ratio level (COMPRESS_HIGH): the frame of fse_tables=True with sequences from
-    two match tables, repeat-offset matches and a lazy parse; with checksum alone."""
+    two match tables, repeat-offset matches and a lazy parse; with checksum alone.  high_split=True: that level with the segments of
+    one buffer (compress_split_segment() bytes each) on many workgroups (COMPRESS_HIGH_SPLIT), for few, large buffers; with checksum
+    alone."""
     lens = np.array([len(b) for b in buffers], dtype=np.uint64)
     in_off = np.zeros(len(buffers), dtype=np.uint64)
     if len(buffers) > 1:
@@ -708,15 +719,16 @@ def compress_batch_host(buffers, ctx: Context, checksum: bool = False, split: bo
         out_off[1:] = np.cumsum(caps[:-1])
     out = np.zeros(max(int(caps.sum()), 1), dtype=np.uint8)
     res = ctx.compress_batch_host(in_base, in_off, lens, out_off, caps, out, checksum=checksum, split=split, fse_tables=fse_tables,
-                                  fast=fast, records=records, fast_split=fast_split, high=high)
+                                  fast=fast, records=records, fast_split=fast_split, high=high, high_split=high_split)
     return [(res[i], out[int(out_off[i]): int(out_off[i]) + int(res[i]["bytes_written"])].tobytes()) for i in range(len(buffers))]
 
 
 def compress_batch_host_dict(buffers, dict_index, ctx: Context, checksum: bool = False, dict_id: bool = True, records: bool = False,
-                             fast_split: bool = False):
+                             fast_split: bool = False, high_split: bool = False):
     """As compress_batch_host, buffer i with dictionary dict_index[i] of ctx.set_compress_dictionaries (COMPRESS_NO_DICT: none;
     dict_index None: every buffer uses the one dictionary set): list of (result record, frame bytes).  records=True: the records
-    level (COMPRESS_RECORDS).  fast_split=True (COMPRESS_FAST_SPLIT) raises CzError: that level takes no dictionary."""
+    level (COMPRESS_RECORDS).  fast_split=True (COMPRESS_FAST_SPLIT) and high_split=True (COMPRESS_HIGH_SPLIT) raise CzError: those levels
+    take no dictionary."""
     lens = np.array([len(b) for b in buffers], dtype=np.uint64)
     in_off = np.zeros(len(buffers), dtype=np.uint64)
     if len(buffers) > 1:
@@ -728,17 +740,18 @@ def compress_batch_host_dict(buffers, dict_index, ctx: Context, checksum: bool =
         out_off[1:] = np.cumsum(caps[:-1])
     out = np.zeros(max(int(caps.sum()), 1), dtype=np.uint8)
     res = ctx.compress_batch_dict_host(in_base, in_off, lens, out_off, caps, out, dict_index, checksum=checksum, dict_id=dict_id, records=records,
-                                       fast_split=fast_split)
+                                       fast_split=fast_split, high_split=high_split)
     return [(res[i], out[int(out_off[i]): int(out_off[i]) + int(res[i]["bytes_written"])].tobytes()) for i in range(len(buffers))]
 
 
 def compress(data, ctx: Context, checksum: bool = False, split: bool = False, fse_tables: bool = False, fast: bool = False,
-             records: bool = False, fast_split: bool = False, high: bool = False) -> bytes:
+             records: bool = False, fast_split: bool = False, high: bool = False, high_split: bool = False) -> bytes:
     """One buffer -> one zstd frame (through the batched kernel; split=True: on many workgroups when it is large; fse_tables=True:
     per-block FSE tables for the sequences; fast=True: the fast level; records=True: the records level; fast_split=True: the fast
-    level on many workgroups when the buffer is large; high=True: the high-ratio level)."""
+    level on many workgroups when the buffer is large; high=True: the high-ratio level; high_split=True: the high-ratio level on many
+    workgroups when the buffer is large)."""
     (r, frame), = compress_batch_host([data], ctx, checksum=checksum, split=split, fse_tables=fse_tables, fast=fast, records=records,
-                                      fast_split=fast_split, high=high)
+                                      fast_split=fast_split, high=high, high_split=high_split)
     if int(r["status"]):
         raise CzError(int(r["status"]), "cz_compress_batch_host")
     return frame

@@ -31,6 +31,7 @@ COMPRESS_FAST = 32                      # the fast level: 32 KiB blocks that sta
 COMPRESS_RECORDS = 64                   # the records level: one wave per record of at most compress_record_max(), with or without dictionaries
 COMPRESS_FAST_SPLIT = 128              # the fast level with the 128 KiB groups of one buffer on many workgroups: the COMPRESS_FAST frame, byte for byte (with the checksum only)
 COMPRESS_HIGH = 256                    # the high-ratio level: the COMPRESS_FSE_TABLES frame with sequences from two match tables, repeat-offset matches and a lazy parse (with the checksum only)
+COMPRESS_HIGH_SPLIT = 512              # the high-ratio level with the segments of one buffer on many workgroups, still one frame; a buffer of at most one segment gives the COMPRESS_HIGH frame (with the checksum only)
 COMPRESS_NO_DICT = 0xFFFFFFFF           # dict_index entry: no dictionary for this buffer
 SEEKABLE_CHECKSUMS = 1                  # cz_seekable_pack_*: the seek table's entries carry the frames' checksums
 # cz_seekable_info (56 bytes)
@@ -62,7 +63,7 @@ class BlockHeader(C.Structure):
 
 def build(force: bool = False) -> str:
     """Compile the library in-tree with hipcc for gfx950 (csrc/Makefile)."""
-    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_enc.hip", "czstd_encsplit.hip", "czstd_encfse.hip", "czstd_enchigh.hip", "czstd_encfast.hip", "czstd_encfastsplit.hip", "czstd_encrec.hip", "czstd_train.hip", "czstd_seekable.hip", "czstd_seekable_host.h", "czstd_seekable_read.hip", "czstd_seekable_read_host.h", "czstd_types.h", "czstd_dict.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("czstd_host.hip", "czstd_kernels.hip", "czstd_chain.hip", "czstd_pre.hip", "czstd_wexec.hip", "czstd_enc.hip", "czstd_encsplit.hip", "czstd_encfse.hip", "czstd_enchigh.hip", "czstd_enchighsplit.hip", "czstd_encfast.hip", "czstd_encfastsplit.hip", "czstd_encrec.hip", "czstd_train.hip", "czstd_seekable.hip", "czstd_seekable_host.h", "czstd_seekable_read.hip", "czstd_seekable_read_host.h", "czstd_types.h", "czstd_dict.h")]
     srcs += [os.path.join(_HERE, "..", "include", f) for f in ("cairo_zstd_amd.h", "cairo_zstd_amd_status.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:

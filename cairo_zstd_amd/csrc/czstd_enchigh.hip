@@ -61,7 +61,10 @@ __device__ static inline uint32_t czh_rep(const uint8_t* in, uint32_t p, uint32_
     return best;
 }
 
-/* czf_block with the match pass, the parse and the repeat offsets of this level.  Always inlined, as czf_block is. */
+/* czf_block with the match pass, the parse and the repeat offsets of this level.  Always inlined, as czf_block is.  MU and FU are the
+   USER of the helpers it calls (cze_match and cze_literals; czf_sequences): a second kernel around it (czstd_enchighsplit.hip) takes
+   values of its own, so that the helpers of the kernel below keep their one caller. */
+template <int MU = 4, int FU = 1>
 __device__ static __forceinline__ uint32_t czh_block(const uint8_t* in, uint32_t b0, uint32_t b1, uint32_t last, uint8_t* st, uint8_t* lit, CzeSeq* seqs,
                                      uint32_t* hufw, uint8_t* fscr) {
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
@@ -89,16 +92,16 @@ __device__ static __forceinline__ uint32_t czh_block(const uint8_t* in, uint32_t
             if (valid) {
                 const uint32_t lo = t > CZE_BACK ? t - CZE_BACK : 0;
                 for (int j = (int)t - 1; j >= (int)lo; j--) if (cze.chash[j] == h) {
-                    const uint32_t m = cze_match<4>(in, p, c0 + (uint32_t)j, b1);
+                    const uint32_t m = cze_match<MU>(in, p, c0 + (uint32_t)j, b1);
                     if (m >= 4) { mlen = m; moff = t - (uint32_t)j; }
                     break;
                 }
                 if (old && p - (old - 1) <= CZE_WINDOW) {               /* further than any in-chunk candidate: longer only */
-                    const uint32_t m = cze_match<4>(in, p, old - 1, b1);
+                    const uint32_t m = cze_match<MU>(in, p, old - 1, b1);
                     if (m >= 4 && m > mlen) { mlen = m; moff = p - (old - 1); }
                 }
                 if (old8 && old8 != old && p - (old8 - 1) <= CZE_WINDOW) {
-                    const uint32_t m = cze_match<4>(in, p, old8 - 1, b1), o = p - (old8 - 1);
+                    const uint32_t m = cze_match<MU>(in, p, old8 - 1, b1), o = p - (old8 - 1);
                     if (m >= 4 && (m > mlen || (m == mlen && o < moff))) { mlen = m; moff = o; }
                 }
                 atomicMax(&cze.htab[h], p + 1);
@@ -158,10 +161,10 @@ __device__ static __forceinline__ uint32_t czh_block(const uint8_t* in, uint32_t
             for (uint32_t k = lane; k < n; k += 64) lit[dst + k] = in[src + k];
         }
         __syncthreads();
-        const uint32_t lsz = cze_literals<false, 4>(lit, nlit, blk, hufw, nullptr, 0u, nullptr);
+        const uint32_t lsz = cze_literals<false, MU>(lit, nlit, blk, hufw, nullptr, 0u, nullptr);
         if (lsz < bsize) {
             __syncthreads();                                            /* the literals' streams have left hufw */
-            csize = lsz + czf_sequences<1>(seqs, nseq, nsl, blk + lsz, bsize - lsz, hufw, fscr);
+            csize = lsz + czf_sequences<FU>(seqs, nseq, nsl, blk + lsz, bsize - lsz, hufw, fscr);
             if (csize < bsize) btype = 2;
         }
         if (btype != 2) {                                               /* the decoder will not see these sequences */

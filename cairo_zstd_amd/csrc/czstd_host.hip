@@ -37,6 +37,7 @@
 #include "czstd_encsplit.hip" /* cz_compress_plan_kernel, cz_compress_segments_kernel (CZ_COMPRESS_SPLIT) */
 #include "czstd_encfse.hip"   /* cz_compress_frames_fse_kernel, cz_compress_segments_fse_kernel (CZ_COMPRESS_FSE_TABLES) */
 #include "czstd_enchigh.hip"  /* cz_compress_frames_high_kernel (CZ_COMPRESS_HIGH) */
+#include "czstd_enchighsplit.hip" /* cz_compress_segments_high_kernel (CZ_COMPRESS_HIGH_SPLIT) */
 #include "czstd_encfast.hip"  /* cz_compress_frames_fast_kernel (CZ_COMPRESS_FAST) */
 #include "czstd_encfastsplit.hip" /* cz_compress_fast_plan_kernel, cz_compress_groups_fast_kernel (CZ_COMPRESS_FAST_SPLIT) */
 #include "czstd_encrec.hip"   /* cz_compress_records_kernel, cz_compress_records_dict_kernel (CZ_COMPRESS_RECORDS) */
@@ -79,7 +80,7 @@ struct cz_dictionary {
 /* One scratch of the compress kernels: `slots` workgroups' worth, and per kernel that runs on it (the second: the kernel with
    dictionaries) as many workgroups as the device holds at once, asked of the occupancy API on first use. */
 struct cz_enc_level { uint8_t* scratch = nullptr; int slots = 0; int grid[2] = {0, 0}; };
-enum { CZ_ENC_PLAIN, CZ_ENC_SPLIT, CZ_ENC_FSE, CZ_ENC_SPLIT_FSE, CZ_ENC_FAST, CZ_ENC_RECORDS, CZ_ENC_FAST_SPLIT, CZ_ENC_HIGH, CZ_ENC_LEVELS };
+enum { CZ_ENC_PLAIN, CZ_ENC_SPLIT, CZ_ENC_FSE, CZ_ENC_SPLIT_FSE, CZ_ENC_FAST, CZ_ENC_RECORDS, CZ_ENC_FAST_SPLIT, CZ_ENC_HIGH, CZ_ENC_HIGH_SPLIT, CZ_ENC_LEVELS };
 struct cz_context {
     int device = 0;
     hipStream_t stream = nullptr; bool own_stream = false;
@@ -1018,9 +1019,10 @@ static int cz_enc_launch(cz_context* c, const cz_enc_batch& b, cz_enc_level& l, 
     return CZ_OK;
 }
 
-/* the flags cz_compress_batch_device / _host take: CZ_COMPRESS_FAST, CZ_COMPRESS_RECORDS, CZ_COMPRESS_FAST_SPLIT and CZ_COMPRESS_HIGH
-   each go with the checksum alone */
+/* the flags cz_compress_batch_device / _host take: CZ_COMPRESS_FAST, CZ_COMPRESS_RECORDS, CZ_COMPRESS_FAST_SPLIT, CZ_COMPRESS_HIGH and
+   CZ_COMPRESS_HIGH_SPLIT each go with the checksum alone */
 static bool cz_compress_flags_ok(uint32_t flags) {
+    if (flags & CZ_COMPRESS_HIGH_SPLIT) return !(flags & ~(CZ_COMPRESS_HIGH_SPLIT | CZ_COMPRESS_CHECKSUM));
     if (flags & CZ_COMPRESS_HIGH) return !(flags & ~(CZ_COMPRESS_HIGH | CZ_COMPRESS_CHECKSUM));
     if (flags & CZ_COMPRESS_FAST_SPLIT) return !(flags & ~(CZ_COMPRESS_FAST_SPLIT | CZ_COMPRESS_CHECKSUM));
     if (flags & ~(CZ_COMPRESS_CHECKSUM | CZ_COMPRESS_SPLIT | CZ_COMPRESS_FSE_TABLES | CZ_COMPRESS_FAST | CZ_COMPRESS_RECORDS)) return false;
@@ -1048,6 +1050,8 @@ CZ_EXPORT int cz_compress_batch_device(cz_context* c, const void* d_in_base, con
         return cz_enc_launch(c, b, l[CZ_ENC_SPLIT], 0, CZE_SPLIT_SCRATCH_BYTES, all, cz_compress_segments_kernel, cz_compress_plan_kernel);
     if (flags & CZ_COMPRESS_FAST_SPLIT)
         return cz_enc_launch(c, b, l[CZ_ENC_FAST_SPLIT], 0, CZE_FAST_SCRATCH_BYTES, all, cz_compress_groups_fast_kernel, cz_compress_fast_plan_kernel);
+    if (flags & CZ_COMPRESS_HIGH_SPLIT)
+        return cz_enc_launch(c, b, l[CZ_ENC_HIGH_SPLIT], 0, CZE_FSE_SPLIT_SCRATCH_BYTES, all, cz_compress_segments_high_kernel, cz_compress_plan_kernel);
     if (flags & CZ_COMPRESS_HIGH) return cz_enc_launch(c, b, l[CZ_ENC_HIGH], 0, CZE_HIGH_SCRATCH_BYTES, n, cz_compress_frames_high_kernel);
     if (flags & CZ_COMPRESS_FSE_TABLES) return cz_enc_launch(c, b, l[CZ_ENC_FSE], 0, CZE_FSE_SCRATCH_BYTES, n, cz_compress_frames_fse_kernel);
     if (flags & CZ_COMPRESS_FAST) return cz_enc_launch(c, b, l[CZ_ENC_FAST], 0, CZE_FAST_SCRATCH_BYTES, n, cz_compress_frames_fast_kernel);

@@ -534,10 +534,34 @@ uint64_t cz_compress_record_max(void);   /* 32768: the largest input CZ_COMPRESS
  * parse that gives up a short match for a longer one at one of the next two positions.  Offsets stay within 1 MiB.  The bytes
  * depend on the input and the flags alone, never on the batch, the grid or timing.  The result flags carry the bit whenever it was
  * requested.  The value is 256: 8 stays an unknown bit.  CZ_E_INVALID_ARG together with CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES,
- * CZ_COMPRESS_FAST, CZ_COMPRESS_RECORDS or CZ_COMPRESS_FAST_SPLIT and in cz_compress_batch_dict_*: the split and dictionary forms
- * of the level are left for later.
+ * CZ_COMPRESS_FAST, CZ_COMPRESS_RECORDS or CZ_COMPRESS_FAST_SPLIT and in cz_compress_batch_dict_*: the split form of the level has
+ * a flag of its own (CZ_COMPRESS_HIGH_SPLIT), the dictionary form is left for later.
  */
 #define CZ_COMPRESS_HIGH 256u
+/*
+ * CZ_COMPRESS_HIGH_SPLIT (cz_compress_batch_device / _host only, alone or with CZ_COMPRESS_CHECKSUM): the
+ * high-ratio level for few, large buffers.  An input longer than S = cz_compress_split_segment() bytes is cut into segments of S
+ * bytes, which different workgroups compress at the same time into ONE standard frame.  The frame is CZ_COMPRESS_HIGH's in
+ * everything but the sequences of later segments: the same header, blocks of at most 128 KiB each Raw, RLE or Compressed by size,
+ * the same literals, per block and field Predefined, RLE or FSE_Compressed mode by exact size, never Repeat_Mode or Treeless
+ * literals, Last_Block on the final block only; cz_compress_bound holds, offsets stay within 1 MiB, and an input of 0xFFF00000
+ * bytes or more is CZ_E_INVALID_ARG.  An input of at most S bytes comes out byte for byte as with CZ_COMPRESS_HIGH; for a longer
+ * one, segment 0 (the header and the blocks of the first S bytes) is byte for byte that frame's.  A later segment starts from
+ * empty tables, into both of which the W input bytes in front of it are inserted (W as for CZ_COMPRESS_SPLIT; the 8-byte table
+ * for positions with 8 bytes left in the input), so its matches reach back into the overlap and no further; and from an offset
+ * history of (0, 0, 0), which equals no offset: its first sequence is written in full, and all six repeat-offset cases are used as
+ * entries become known (what a segment knows is always a prefix of the decoder's history).  A block that is not written
+ * Compressed leaves the history as it found it.  The bytes depend on the input and the flags alone, never on the batch, the grid
+ * or timing.  CZ_E_OUTPUT_TOO_SMALL ends the frame at a block boundary: bytes_written, bytes_read and blocks cover the whole
+ * blocks placed, and nothing past bytes_written is touched.  CZ_E_WAIT_EXPIRED is possible, as described for CZ_COMPRESS_SPLIT.
+ * The result flags carry the bit whenever it was requested, whatever the input length.  An input of at most S bytes is one unit
+ * of work: for batches of very many such buffers CZ_COMPRESS_HIGH does the same work without the plan launch and the search per
+ * unit.
+ * The value is 512, a bit of its own (CZ_COMPRESS_HIGH | CZ_COMPRESS_SPLIT stays CZ_E_INVALID_ARG; 8 stays an unknown bit).
+ * CZ_E_INVALID_ARG together with any other flag but the checksum, CZ_COMPRESS_HIGH and CZ_COMPRESS_SPLIT included, and in
+ * cz_compress_batch_dict_*.
+ */
+#define CZ_COMPRESS_HIGH_SPLIT 512u
 /* One per buffer, written by the device. */
 typedef struct cz_compress_result {
     int32_t  status;            /* CZ_OK | CZ_E_OUTPUT_TOO_SMALL | CZ_E_INVALID_ARG (an input of 4 GiB - 1 MiB or more) | CZ_E_WAIT_EXPIRED */
@@ -552,7 +576,7 @@ typedef struct cz_compress_result {
  * every byte of its own region past bytes_written untouched.  out_cap[i] = cz_compress_bound(in_len[i]) always suffices.
  * flags: CZ_COMPRESS_CHECKSUM, CZ_COMPRESS_SPLIT, CZ_COMPRESS_FSE_TABLES, CZ_COMPRESS_FAST (not with the two before it),
  * CZ_COMPRESS_RECORDS (not with the three before it), CZ_COMPRESS_FAST_SPLIT (with the checksum only), CZ_COMPRESS_HIGH (with the
- * checksum only); any other bit is CZ_E_INVALID_ARG. */
+ * checksum only), CZ_COMPRESS_HIGH_SPLIT (with the checksum only); any other bit is CZ_E_INVALID_ARG. */
 int cz_compress_batch_device(cz_context* ctx, const void* d_in_base, const uint64_t* d_in_off, const uint64_t* d_in_len, size_t n,
                              void* d_out_base, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint32_t flags,
                              cz_compress_result* d_results);

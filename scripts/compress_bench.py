@@ -14,6 +14,8 @@ CAIRO_ZSTD_AMD_LIB; --tag goes into every row to tell them apart.
 
 --high measures CZ_COMPRESS_HIGH next to CZ_COMPRESS_FSE_TABLES and libzstd levels 1, 3 and 6 (DESIGN.md §10.8;
 profiles/compress/high_bench.json).
+--high-split measures CZ_COMPRESS_HIGH_SPLIT next to CZ_COMPRESS_HIGH and CZ_COMPRESS_SPLIT | CZ_COMPRESS_FSE_TABLES in one session, with
+the fastest and slowest run of each, and libzstd levels 3 and 6 (profiles/compress/high_split_bench.json).
 --fse-tables measures CZ_COMPRESS_FSE_TABLES: every batch unsplit and split, each without and with the flag in
 the same session, and the frame bytes of the 69 corpus originals without and with it; --out defaults to
 profiles/compress/fse_bench.json."""
@@ -43,7 +45,8 @@ def tiled(n, size, seed):
     return [pool[int(s):int(s) + size] for s in starts]
 
 
-def device_run(cz, ctx, stream, bufs, runs, split=False, fse=False, high=False):
+def device_run(cz, ctx, stream, bufs, runs, split=False, fse=False, high=False, high_split=False, spread=False):
+    """(median ms of `runs` launches after one warm-up, frame bytes); with `spread` also the fastest and the slowest run."""
     import torch
     dev = torch.device("cuda:0")
     lens = np.array([len(b) for b in bufs], dtype=np.uint64)
@@ -63,13 +66,16 @@ def device_run(cz, ctx, stream, bufs, runs, split=False, fse=False, high=False):
         e0.record(stream)
         ctx.compress_batch_device(d_in.data_ptr(), desc[0].data_ptr(), desc[1].data_ptr(), len(bufs), d_out.data_ptr(),
                                   desc[2].data_ptr(), desc[3].data_ptr(), d_res.data_ptr(), **(dict(split=True) if split else {}),
-                                  **(dict(fse_tables=True) if fse else {}), **(dict(high=True) if high else {}))
+                                  **(dict(fse_tables=True) if fse else {}), **(dict(high=True) if high else {}),
+                                  **(dict(high_split=True) if high_split else {}))
         e1.record(stream)
         e1.synchronize()
         if r:
             times.append(e0.elapsed_time(e1))
     res = d_res.cpu().numpy().view(cz.COMPRESS_RESULT_DTYPE)
     assert (res["status"] == 0).all()
+    if spread:
+        return float(np.median(times)), int(res["bytes_written"].sum()), float(min(times)), float(max(times))
     return float(np.median(times)), int(res["bytes_written"].sum())
 
 
@@ -133,6 +139,40 @@ def high_bench(args, cz, ctx, stream, device):
         json.dump(rows, f, indent=1)
 
 
+def high_split_bench(args, cz, ctx, stream, device):
+    """CZ_COMPRESS_HIGH, CZ_COMPRESS_HIGH_SPLIT and CZ_COMPRESS_SPLIT | CZ_COMPRESS_FSE_TABLES in one session on 64 x 2 MiB, 1 x 16 MiB and
+    10 000 x 128 KiB: kernel time (median, fastest and slowest of --runs after a warm-up) and frame bytes; libzstd levels 3 and 6 on
+    --threads CPUs.  Every row says how much faster the split form is and whether its slowest run is below the unsplit form's fastest."""
+    out = args.out or os.path.join(ROOT, "profiles", "compress", "high_split_bench.json")
+    rows = []
+    for name, n, size in (("64x2MiB", 64, 2 << 20), ("1x16MiB", 1, 16 << 20), ("10000x128KiB", 10000, 128 << 10)):
+        bufs = tiled(n, size, seed=1)
+        nbytes = n * size
+        row = dict(batch=name, input_bytes=nbytes, device=device, runs=args.runs, segment=cz.compress_split_segment())
+        for key, kw in (("high", dict(high=True)), ("high_split", dict(high_split=True)), ("split_fse_tables", dict(split=True, fse=True)),
+                        ("high_again", dict(high=True))):
+            ms, written, lo, hi = device_run(cz, ctx, stream, bufs, args.runs, spread=True, **kw)
+            row[key] = dict(device_ms=round(ms, 3), min_ms=round(lo, 3), max_ms=round(hi, 3), device_gbps=round(nbytes / ms / 1e6, 2),
+                            device_ratio=round(nbytes / written, 4), frame_bytes=written)
+        h_lo = min(row["high"]["min_ms"], row["high_again"]["min_ms"])
+        h_hi = max(row["high"]["max_ms"], row["high_again"]["max_ms"])
+        row["high_over_high_split"] = round(row["high"]["device_ms"] / row["high_split"]["device_ms"], 3)
+        row["high_split_slowest_below_high_fastest"] = row["high_split"]["max_ms"] < h_lo
+        row["high_split_within_high_spread"] = h_lo <= row["high_split"]["device_ms"] <= h_hi
+        for level in (() if args.no_libzstd else (3, 6)):
+            cpu = libzstd_run(bufs, args.threads, args.runs, level)
+            if cpu:
+                row[f"libzstd_{level}"] = dict(threads=args.threads, ms=round(cpu[0], 3), gbps=round(nbytes / cpu[0] / 1e6, 2), ratio=round(nbytes / cpu[1], 4),
+                                               frame_bytes=cpu[1])
+        if args.tag:
+            row["tag"] = args.tag
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(rows, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -142,6 +182,7 @@ def main():
     ap.add_argument("--pieces", action="store_true", help="also: the 64 x 2 MiB batch as 1 024 frames of 128 KiB (frame bytes)")
     ap.add_argument("--fse-tables", action="store_true", help="measure CZ_COMPRESS_FSE_TABLES next to the same launches without it")
     ap.add_argument("--high", action="store_true", help="measure CZ_COMPRESS_HIGH next to CZ_COMPRESS_FSE_TABLES, and libzstd levels 1, 3 and 6")
+    ap.add_argument("--high-split", action="store_true", help="measure CZ_COMPRESS_HIGH_SPLIT next to CZ_COMPRESS_HIGH and CZ_COMPRESS_SPLIT | CZ_COMPRESS_FSE_TABLES")
     ap.add_argument("--no-libzstd", action="store_true")
     ap.add_argument("--tag", default=None, help="free text copied into every row")
     args = ap.parse_args()
@@ -161,6 +202,10 @@ def main():
         rows.append(row)
     if args.high:
         high_bench(args, cz, ctx, stream, torch.cuda.get_device_name(0))
+        ctx.close()
+        return
+    if args.high_split:
+        high_split_bench(args, cz, ctx, stream, torch.cuda.get_device_name(0))
         ctx.close()
         return
     variants = [(s, f) for s in (False, True) for f in (False, True)] if args.fse_tables else [(args.split, False)]
